@@ -25,7 +25,14 @@ whole job takes at that rate).
 Job mode (workloads c2, small, c3, c5, ...: the other BASELINE configs, development aids): a step is the
 whole job, pairs sharded over ranks, "scaling" "strong" (the round-1 bench line for C2 is kept in profiles/).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c4small|c4job|c2|small|c3|c5|c3small|c5small|c5mid] [--no-cpu-baseline]
+A plain run sets up, warms up, times the K steps, writes the outputs if --dump-outputs is given and prints the line.
+--full adds what takes work of its own outside the timed steps: the stand-alone seed scan (roofline.frac_standalone),
+the probe for the reference's tools (reference_tools) and the CPU baseline (cpu_baseline; --no-cpu-baseline drops it).
+--dump-outputs DIR writes what the last timed step computed, one float64 DIR/<array>_<field>.npy per record field
+(dump_outputs).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c4small|c4job|c2|small|c3|c5|c3small|c5small|c5mid]
+                    [--full [--no-cpu-baseline]] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -273,13 +280,38 @@ def standalone_seed_scan(engine, A, tq):
             'frac': b_alg / (ms / 1e3) / 8e12 if ms > 0 else None}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: every record array of `arrays` (name -> structured array) as one float64 file per field,
+    `path`/<name>_<field>.npy (every field is an integer that float64 holds exactly).  Rows are put in lexicographic
+    order of all fields first, so that two builds compare output for output whatever order the engine returns them
+    in; an array whose files would take more than its share of 64 MB keeps a seeded sample of its rows, the same rows
+    in every field."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // max(1, len(arrays))
+    for name, rec in arrays.items():
+        fields = [f for f in rec.dtype.names if f != 'reserved']
+        if rec.size:
+            rec = rec[np.lexsort([rec[f] for f in reversed(fields)])]
+        keep = budget // (8 * len(fields))
+        if rec.size > keep:
+            rec = rec[np.sort(np.random.Generator(np.random.PCG64(seed)).choice(rec.size, keep, replace=False))]
+        for f in fields:
+            np.save(os.path.join(path, '%s_%s.npy' % (name, f)), rec[f].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=8)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', default='c4', choices=sorted(WORKLOADS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also the measurements outside the timed steps: stand-alone seed scan, '
+                    'reference tools probe, CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/*.npy (float64)')
     ap.add_argument('--emulate', default=None, help='job mode, R/N: time the shard rank R of N would get, on this one GPU, without communication (development aid)')
     args = ap.parse_args()
 
@@ -383,8 +415,11 @@ def main():
     dt = dist.max_float(time.time() - t0)
     ms_per_step = 1000.0 * dt / max(1, args.steps)
 
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, {'records' if kind == 'row' else 'alignments': alns, 'regions': regions})
+
     standalone = None
-    if dist.rank == 0 and B is None and nscaf > 1:
+    if args.full and dist.rank == 0 and B is None and nscaf > 1:
         try:
             standalone = standalone_seed_scan(engine, A, (0, 1))
         except Exception as e:   # the calibration must never cost the bench line
@@ -435,8 +470,7 @@ def main():
                          'note': 'achieved / peak / frac = the HBM roofline SURVEY 8(d) defines: B_scan per unit / HIP-event duration of the launch / 8 TB/s.  '
                                  'The fused kernel never writes the hit array that byte model charges for; what bounds it is VALU issue of the '
                                  'pre-filter (bound = valu; the valu block: instructions per launch x cycles per instruction of its opcode mix / '
-                                 'issue time of the 1024 SIMDs).  traffic_frac is what it really moves; frac_standalone is the seed scan alone (K3).',
-                         'frac_standalone': standalone},
+                                 'issue time of the 1024 SIMDs).  traffic_frac is what it really moves; frac_standalone (--full) is the seed scan alone (K3).'},
             'stage_ms_per_step_rank0': {k: round(agg[k] / max(1, args.steps), 3) for k in ('ms_index', 'ms_scan', 'ms_scan_fill', 'ms_extend', 'ms_chain', 'ms_gapped', 'ms_total')},
             'stage_note': 'ms_scan = heavy phase (K34 + the walk-queue kernel per unit), ms_scan_fill = the K34 launches alone, ms_extend = tails once per batch; K34 timed region includes nothing else: inputs (packed genome, seed indexes of the other scaffolds) are resident in HBM, the H2D of the genome (1 GB, ~16 ms + 6 ms K1 per 50 s job) is outside',
             'counts_per_step_rank0': {k: int(agg[k] // max(1, args.steps)) for k in ('seed_hits', 'walked_hits', 'followers', 'hsps', 'chained_hsps', 'alignments', 'batches', 'queue_reruns')},
@@ -444,9 +478,11 @@ def main():
         }
         if kind == 'row':
             line['whole_job_s_at_this_rate'] = total_bp / 1e9 / value
-        line['reference_tools'] = reference_tools_check()
-        if not args.no_cpu_baseline and dist.world == 1 and B is None:
-            line['cpu_baseline'] = cpu_baseline_rows(seqs) if kind == 'row' and nscaf > 1 else cpu_baseline_job(names, seqs, (0, 0), (0, 1))
+        if args.full:
+            line['roofline']['frac_standalone'] = standalone
+            line['reference_tools'] = reference_tools_check()
+            if not args.no_cpu_baseline and dist.world == 1 and B is None:
+                line['cpu_baseline'] = cpu_baseline_rows(seqs) if kind == 'row' and nscaf > 1 else cpu_baseline_job(names, seqs, (0, 0), (0, 1))
         print(json.dumps(line))
     A.close()
     if B is not None:

@@ -10,7 +10,7 @@ this repo's drop-in (`python -m mimeo_amd.lastz_shim`, same argv), and diffs the
     python scripts/crosscheck_lastz.py [--json] [--cases N] [--lzpath lastz]
 
 Without a lastz binary it prints "lastz absent: parity unpinned" and exits 0 (nothing is run, no GPU is
-touched).  bench.py calls `probe()` and records which of the two happened in its JSON line.
+touched).  bench.py --full calls `probe()` and records which of the two happened in its JSON line.
 """
 import argparse
 import json

@@ -84,6 +84,37 @@ def test_bench_a11_filter_matches_the_printed_identity_rule():
     assert list(got['score']) == exp and 0 < len(exp) < a.size
 
 
+def test_bench_dump_outputs_writes_every_field_in_a_fixed_order(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 file per record field, rows in lexicographic order whatever order they came in, and an
+    array over its share of the 64 MB cut to the same seeded sample of rows on every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from mimeo_amd import _ffi
+    rng = np.random.default_rng(9)
+    a = np.zeros(3000, dtype=_ffi.ALIGNMENT)
+    for f in ('tid', 'qid', 'tstart', 'tend', 'qstart', 'qend', 'id_n', 'id_d', 'qstrand'):
+        a[f] = rng.integers(0, 50, a.size)
+    a['score'] = rng.integers(-(1 << 40), 1 << 40, a.size)
+    r = np.zeros(500, dtype=_ffi.INTERVAL)
+    r['chrom'], r['start'], r['end'] = rng.integers(0, 4, r.size), rng.integers(0, 1 << 31, r.size), rng.integers(0, 1 << 32, r.size)
+    bench.dump_outputs(str(tmp_path / 'x'), {'records': a, 'regions': r})
+    bench.dump_outputs(str(tmp_path / 'y'), {'records': a[::-1].copy(), 'regions': r[::-1].copy()})
+    names = sorted(os.listdir(tmp_path / 'x'))
+    assert names == sorted(os.listdir(tmp_path / 'y')) and len(names) == 13 and 'records_reserved.npy' not in names
+    for n in names:
+        x, y = np.load(tmp_path / 'x' / n), np.load(tmp_path / 'y' / n)
+        assert x.dtype == np.float64 and np.array_equal(x, y)
+    got = np.rec.fromarrays([np.load(tmp_path / 'x' / ('records_%s.npy' % f)) for f in a.dtype.names if f != 'reserved'])
+    exp = np.sort(np.rec.fromarrays([a[f].astype(np.float64) for f in a.dtype.names if f != 'reserved']))
+    assert np.array_equal(got, exp)
+    assert np.array_equal(np.load(tmp_path / 'x' / 'regions_end.npy'), np.sort(r, order=['chrom', 'start', 'end'])['end'].astype(np.float64))
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 2 * 100 * 8 * 10)   # room for 100 of the 3000 records
+    bench.dump_outputs(str(tmp_path / 's1'), {'records': a, 'regions': r})
+    bench.dump_outputs(str(tmp_path / 's2'), {'records': a[::-1].copy(), 'regions': r})
+    s1, s2 = np.load(tmp_path / 's1' / 'records_score.npy'), np.load(tmp_path / 's2' / 'records_score.npy')
+    assert s1.size == 100 and np.array_equal(s1, s2) and set(s1) <= set(exp['f6'])
+
+
 WORKER = textwrap.dedent('''
     import os, sys
     sys.path.insert(0, %r)

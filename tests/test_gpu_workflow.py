@@ -194,6 +194,37 @@ def test_bench_under_rccl_single_rank(tmp_path):
     assert b['n_gpus'] == 1 and b['scaling'] == 'weak' and b['result']['records_kept'] > 0 and b['result']['regions'] > 0
 
 
+def test_bench_plain_and_full_runs_dump_the_same_outputs(tmp_path):
+    """A plain run prints the headline line without the measurements of --full (stand-alone seed scan, tools probe, CPU
+    baseline); --dump-outputs writes the last step's kept records and the regions, and a second run of the same
+    arguments, here with --full, writes the same files."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dirs = [], []
+    for k, extra in enumerate(([], ['--full', '--no-cpu-baseline'])):
+        d = tmp_path / ('out%d' % k)
+        run = subprocess.run([sys.executable, 'bench.py', '--workload', 'c4small', '--steps', '1', '--warmup', '0',
+                              '--dump-outputs', str(d)] + extra, cwd=root, capture_output=True, text=True, timeout=600)
+        assert run.returncode == 0, run.stderr[-3000:]
+        lines.append(json.loads(run.stdout.strip().split('\n')[-1]))
+        dirs.append(d)
+    plain, full = lines
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in plain and key in full
+    assert plain['steps'] == 1 and plain['ms_per_step'] > 0
+    assert 'reference_tools' not in plain and 'cpu_baseline' not in plain and 'frac_standalone' not in plain['roofline']
+    assert 'reference_tools' in full and full['roofline']['frac_standalone']['avg_launch_ms'] > 0
+    assert plain['result'] == full['result'] and plain['result']['records_kept'] > 0 and plain['result']['regions'] > 0
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and 'records_tstart.npy' in names and 'regions_end.npy' in names
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        assert a.size == plain['result']['records_kept' if n.startswith('records_') else 'regions']
+
+
 def test_lastz_shim_runs_the_reference_invocation(eng, tmp_path):
     """The literal argv the reference builds for lastz (wrappers.py:1025-1037) -> 13-field general
     rows that the reference's own awk filter turns into the same TAB block as the oracle."""
