@@ -238,7 +238,7 @@ struct ExtBatch {
     double expect_hits_ = 0, shrink_ = 1.0;
     uint32_t ebits_ = 0, dbits_ = 0, key_bits_ = 0;
     bool v1_ = false, started_ = false, k4_stats_ = false, splittable_ = false;
-    uint32_t k34_dbg_ = 0, qw_blocks_ = 256;
+    uint32_t k34_dbg_ = 0;
     int k4_variant_ = 0;
     void *q_ = nullptr;   // ExtQueues of the batch (k4_device.h), owned
     int enqueue_heavy();

@@ -33,14 +33,6 @@
 
 namespace mimeo {
 
-// the form of the first pass = bits 5 and 6 of the switch word (do_tile).  scripts/k34_isa_mix.py compiles ONE form alone
-// (-DK34_ONLY_FORM=0) to read its ISA: the blocks of the form that does not run would dilute the opcode mix it prices.
-#ifdef K34_ONLY_FORM
-#define K34_FORM(dbg) ((uint32_t)(K34_ONLY_FORM))
-#else
-#define K34_FORM(dbg) ((dbg) & 96u)
-#endif
-
 constexpr uint32_t TCH = 64;      // target entries per wavefront and chunk: one per lane
 constexpr uint32_t DQ = 192;      // pair descriptors per wavefront and round
 constexpr uint32_t CARE10 = 0x1A997u;  // offsets 0 1 2 4 7 8 11 13 15 16 of CARE19
@@ -62,8 +54,7 @@ struct FusedArgs {
     HeavyPlan plan;
     int xdrop, hspthresh, transitions;
     uint32_t dbg;  // switch word.  Development (MIMEO_K34_DEBUG): 1 = no pre-filter arithmetic, 2 = nothing is passed on, 4 = no pair
-                   // rounds, 8 = no descriptors either (lane-major emission), 16 = run members are not dropped; bits 5 and 6 (32, 64) =
-                   // the form of the first pass (MIMEO_K34_FORM, k4_extend.hip)
+                   // rounds, 8 = no descriptors either (split pass only: its lane-major emission), 16 = run members are not dropped
 };
 
 // ---- pre-filter on two frames in the common alignment ------------------------------------------------------
@@ -297,10 +288,10 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
         // A key and its 13 probes differ in one bit, so in the segment of half h an entry whose key lies in h finds ALL its
         // partners there but the one of bit 11, and an entry of the other half only that one: 13 probes per entry and tile
         // instead of 26 (a chunk of one kind takes 12 probes or 1, wave-uniformly; the one mixed chunk of a tile all 13 —
-        // the clamped offsets make every probe right in any segment).  Bit 5 (32) of the switch word: off (tiles cut by entry count).
+        // the clamped offsets make every probe right in any segment).  Other tiles are cut by entry count.
         bool aligned = false;
         uint32_t mid = 0;
-        if (!HEAVY && nQ > QSEG && !(K34_FORM(A.dbg) & 32u)) {
+        if (!HEAVY && nQ > QSEG) {
             mid = (uint32_t)__builtin_amdgcn_readfirstlane((int)((reinterpret_cast<const uint32_t *>(sQF) + TILE_WORDS + 4)[TILE_WORDS / 2] - q0));
             aligned = mid <= QSEG && nQ - mid <= QSEG;   // (then 0 < mid < nQ: both segments hold entries)
         }
@@ -393,13 +384,13 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
                 }
                 const bool tvalid = lane < ne;
                 // my entry's in-tile key from its own frame: hi plane, seed window = frame bits 109 .. 127 (hi3 = f2.y)
-                uint32_t w = 0, c = 0, nmask = 0, dmask = 0;   // dmask (split pass): probes whose range is enumerated densely, below
+                uint32_t w = 0, c = 0, nmask = 0, dmask = 0;   // c, nmask, dmask: the split pass's probe counts (below)
                 if (tvalid) w = pext12(f2.y >> 13);
                 const int nn = A.transitions ? SEED_WEIGHT + 1 : 1;
-                // the probes this chunk needs in this segment: all of them, or — aligned tiles, a chunk whose keys lie in one half of
-                // the key space (all but one chunk of a tile) — the key itself and its partners of bits 0 .. 10 when that is the
-                // segment's half, else the partner of bit 11 alone
-                if (!HEAVY && !(K34_FORM(A.dbg) & 64u)) {
+                if constexpr (!HEAVY) {
+                    // the probes this chunk needs in this segment: all of them, or — aligned tiles, a chunk whose keys lie in one half of
+                    // the key space (all but one chunk of a tile) — the key itself and its partners of bits 0 .. 10 when that is the
+                    // segment's half, else the partner of bit 11 alone
                     int jlo = 0, jhi = nn;
                     if (aligned) {
                         const uint64_t in_half = __ballot(tvalid && (w >> 11) == half), in_other = __ballot(tvalid && (w >> 11) != half);
@@ -413,7 +404,7 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
                     // range holds 0.6 entries on average on a C4 tile, so a probe is two or three levels (the ballot of the next one is
                     // empty).  No prefix sum over the lanes, no second visit of the offsets, no per-lane loop that runs as long as the
                     // busiest lane's: the emission was 20 % of this kernel's time.  The ring holds 128 descriptors: a round of 64 pairs
-                    // runs as soon as 64 are waiting (bit 6 (64) of the switch word: the lane-major emission below, as in the split pass).
+                    // runs as soon as 64 are waiting.
                     constexpr uint32_t RING = 128;
                     static_assert(RING <= DQ, "the ring lives in the wavefront's descriptor queue");
                     const uint32_t l16 = lane << 16;
@@ -462,76 +453,70 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
                         }
                     }
                     if (pend) round(pend);   // the rest of this chunk's pairs
-                    continue;   // next chunk
-                }
-                {
-                    auto probes = [&](const int jlo, const int jhi) {   // (constant bounds: unrolled, the offsets of four probes in flight)
+                } else {
+                    // ---- split pass: every probe's range is counted, and a prefix sum of the counts over the lanes places the
+                    // descriptors lane-major; a range of DENSE_MIN entries or more is enumerated densely instead (dmask, below)
+                    auto probes = [&]() {
                         if (!tvalid) return;
-                        for (int j = jlo; j < jhi; j++) {
+                        for (int j = 0; j < nn; j++) {
                             const uint32_t w2 = j ? (w ^ (1u << (j - 1))) : w;
                             const uint32_t a = sQ[w2], b = sQ[w2 + 1];
-                            if (HEAVY && b - a >= DENSE_MIN) { dmask |= 1u << j; continue; }
+                            if (b - a >= DENSE_MIN) { dmask |= 1u << j; continue; }
                             c += b - a;
                             nmask |= (b != a ? 1u : 0u) << j;
                         }
                     };
-                    const uint64_t in_half = (!HEAVY && aligned) ? __ballot(tvalid && (w >> 11) == half) : 1ull;
-                    const uint64_t in_other = (!HEAVY && aligned) ? __ballot(tvalid && (w >> 11) != half) : 1ull;
-                    if (in_half && in_other) probes(0, nn);
-                    else if (in_half) probes(0, min(nn, SEED_WEIGHT));
-                    else probes(SEED_WEIGHT, nn);
-                }
-                // inclusive prefix sum over the lanes: DPP (VALU latency), not six trips through the LDS crossbar
-                uint32_t inc = c;
-                inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, false);   // row_shr:1
-                inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, false);   // row_shr:2
-                inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, false);   // row_shr:4
-                inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, false);   // row_shr:8
-                inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xa, 0xf, false);   // row_bcast:15
-                inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x143, 0xc, 0xf, false);   // row_bcast:31
-                const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63), st = inc - c;
-                hits_acc += tot;
-                for (uint32_t rb = 0; rb < tot; rb += DQ) {
-                    if (!(A.dbg & 8u) && c && st < rb + DQ && st + c > rb) {
-                        // a probe's range holds one or two entries nearly always (0.3 on average on a C4 tile, the empty ones
-                        // are not in nmask): they are written outright, the loop is for the rest; a range that straddles the
-                        // window of this round is clipped entry by entry
-                        uint32_t acc = st;
-                        const uint32_t wend = rb + DQ;
-                        for (uint32_t m = nmask; m; m &= m - 1u) {
-                            const uint32_t j = (uint32_t)__builtin_ctz(m);
-                            const uint32_t w2 = j ? (w ^ (1u << (j - 1u))) : w;
-                            const uint32_t a = sQ[w2], cnt = (uint32_t)sQ[w2 + 1] - a, d0 = (lane << 16) | a;
-                            if (acc >= rb && acc + cnt <= wend) {
-                                uint32_t *dst = sD + (acc - rb);
-                                dst[0] = d0;
-                                if (cnt > 1) {
-                                    dst[1] = d0 + 1u;
+                    probes();
+                    // inclusive prefix sum over the lanes: DPP (VALU latency), not six trips through the LDS crossbar
+                    uint32_t inc = c;
+                    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, false);   // row_shr:1
+                    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, false);   // row_shr:2
+                    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, false);   // row_shr:4
+                    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, false);   // row_shr:8
+                    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xa, 0xf, false);   // row_bcast:15
+                    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x143, 0xc, 0xf, false);   // row_bcast:31
+                    const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63), st = inc - c;
+                    hits_acc += tot;
+                    for (uint32_t rb = 0; rb < tot; rb += DQ) {
+                        if (!(A.dbg & 8u) && c && st < rb + DQ && st + c > rb) {
+                            // a probe's range holds one or two entries nearly always (0.3 on average on a C4 tile, the empty ones
+                            // are not in nmask): they are written outright, the loop is for the rest; a range that straddles the
+                            // window of this round is clipped entry by entry
+                            uint32_t acc = st;
+                            const uint32_t wend = rb + DQ;
+                            for (uint32_t m = nmask; m; m &= m - 1u) {
+                                const uint32_t j = (uint32_t)__builtin_ctz(m);
+                                const uint32_t w2 = j ? (w ^ (1u << (j - 1u))) : w;
+                                const uint32_t a = sQ[w2], cnt = (uint32_t)sQ[w2 + 1] - a, d0 = (lane << 16) | a;
+                                if (acc >= rb && acc + cnt <= wend) {
+                                    uint32_t *dst = sD + (acc - rb);
+                                    dst[0] = d0;
+                                    if (cnt > 1) {
+                                        dst[1] = d0 + 1u;
 #pragma unroll 1
-                                    for (uint32_t k = 2; k < cnt; k++) dst[k] = d0 + k;
+                                        for (uint32_t k = 2; k < cnt; k++) dst[k] = d0 + k;
+                                    }
+                                } else {
+                                    const uint32_t g0 = max(acc, rb), g1 = min(acc + cnt, wend);
+#pragma unroll 1
+                                    for (uint32_t g = g0; g < g1; g++) sD[g - rb] = d0 + (g - acc);
                                 }
-                            } else {
-                                const uint32_t g0 = max(acc, rb), g1 = min(acc + cnt, wend);
-#pragma unroll 1
-                                for (uint32_t g = g0; g < g1; g++) sD[g - rb] = d0 + (g - acc);
+                                acc += cnt;
                             }
-                            acc += cnt;
                         }
+                        __builtin_amdgcn_wave_barrier();
+                        const uint32_t n = (A.dbg & 4u) ? 0u : min(DQ, tot - rb);   // development: 4 = no pair rounds, 8 = no descriptors either
+                        for (uint32_t i = 0; i < n; i += 64) {
+                            const bool valid = i + lane < n;
+                            const uint32_t d = valid ? sD[i + lane] : 0u;
+                            const uint32_t owner = d >> 16, qi = d & 0xFFFFu;
+                            // the target frame lives in its owner lane's registers, the query frame in LDS
+                            const uint4 ta = bperm4(owner, f0), tb = bperm4(owner, f1), tc = bperm4(owner, f2);
+                            const uint32_t tpf = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(owner << 2), (int)mypos);
+                            pair_round(valid, ta, tb, tc, tpf, qi, qs);
+                        }
+                        __builtin_amdgcn_wave_barrier();
                     }
-                    __builtin_amdgcn_wave_barrier();
-                    const uint32_t n = (A.dbg & 4u) ? 0u : min(DQ, tot - rb);   // development: 4 = no pair rounds, 8 = no descriptors either
-                    for (uint32_t i = 0; i < n; i += 64) {
-                        const bool valid = i + lane < n;
-                        const uint32_t d = valid ? sD[i + lane] : 0u;
-                        const uint32_t owner = d >> 16, qi = d & 0xFFFFu;
-                        // the target frame lives in its owner lane's registers, the query frame in LDS
-                        const uint4 ta = bperm4(owner, f0), tb = bperm4(owner, f1), tc = bperm4(owner, f2);
-                        const uint32_t tpf = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(owner << 2), (int)mypos);
-                        pair_round(valid, ta, tb, tc, tpf, qi, qs);
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                }
-                if (HEAVY) {
                     // Long ranges — a microsatellite's key holds hundreds of the segment's entries, and the split pass is made of
                     // such tiles — are not written out as descriptors: for one target entry at a time (its frame in scalar
                     // registers) the lanes take 64 consecutive query entries of the range, whose frames are conflict-free LDS

@@ -893,19 +893,7 @@ int ExtBatch::start(const std::vector<UnitWork> &work, const mimeo_params *p, co
     // development / test switches: read once per batch, never per launch
     v1_ = getenv("MIMEO_HEAVY") && !strcmp(getenv("MIMEO_HEAVY"), "v1");
     k34_dbg_ = getenv("MIMEO_K34_DEBUG") ? (uint32_t)atoi(getenv("MIMEO_K34_DEBUG")) : 0u;
-    {   // the form of K34's first pass (k34_fused.hip; bits 5 and 6 of its switch word): two-segment tiles cut at the middle key
-        // (0) or by entry count (32); descriptors written level by level (0) or lane-major behind a prefix sum (64).
-        // MIMEO_K34_FORM = level (0) | cut (32) | half (64) | lane (96: the round-2/3 form) picks one (tests, scripts/gpu_k34_ab.py).
-        const char *form = getenv("MIMEO_K34_FORM");
-        if (form && strcmp(form, "level") && strcmp(form, "cut") && strcmp(form, "half") && strcmp(form, "lane")) {
-            set_error(std::string("MIMEO_K34_FORM=") + form + ": not one of level, cut, half, lane");
-            return MIMEO_ERR_ARG;
-        }
-        const uint32_t bits = !form ? K34_FORM_DEFAULT : !strcmp(form, "level") ? 0u : !strcmp(form, "cut") ? 32u : !strcmp(form, "half") ? 64u : 96u;
-        k34_dbg_ = (k34_dbg_ & ~96u) | bits;
-    }
     k4_variant_ = getenv("MIMEO_K4_VARIANT") ? atoi(getenv("MIMEO_K4_VARIANT")) : 0;
-    qw_blocks_ = getenv("MIMEO_QW_BLOCKS") ? (uint32_t)std::max(1, atoi(getenv("MIMEO_QW_BLOCKS"))) : 256u;
     k4_stats_ = getenv("MIMEO_K4_STATS") != nullptr;
     int rc;
     if ((rc = units.reserve((size_t)nunits * sizeof(UnitDesc))) || (rc = ctr.reserve(sizeof(ExtCounters))) ||
@@ -1075,9 +1063,9 @@ int ExtBatch::enqueue_heavy() {
                     ExtQueues qq = q;
                     qq.nwalk_u = q.nwalk_u + (size_t)u0 * 8;
                     const FusedUnit *fu = (const FusedUnit *)funits.p + u0;
-                    // a unit's queue is worked off by at most qw_blocks_ workgroups (their end-of-kernel flushes are same-address
+                    // a unit's queue is worked off by at most 256 workgroups (their end-of-kernel flushes are same-address
                     // atomics: more workgroups cost more than they bring), fewer when many small units share the launch
-                    const uint32_t qblocks = std::max(1u, std::min(qw_blocks_, (8192u + nu - 1) / nu));
+                    const uint32_t qblocks = std::max(1u, std::min(256u, (8192u + nu - 1) / nu));
                     if (slim) hipLaunchKernelGGL(k4_walk_batch<9>, dim3(qblocks, nu), dim3(FAST_THREADS), 0, st, fu, p->xdrop, p->hspthresh, p->transitions, tab, qq);
                     else hipLaunchKernelGGL(k4_walk_batch<5>, dim3(qblocks, nu), dim3(FAST_THREADS), 0, st, fu, p->xdrop, p->hspthresh, p->transitions, tab, qq);
                 }

@@ -3,7 +3,7 @@
 the 12-or-1 probes of a chunk, the level-by-level emission into the ring of 128 descriptors, the rounds of 64 — against the pairs a
 brute-force join of the tile gives (mimeo_amd/csrc/k34_fused.hip: do_tile, "level emission").  What it checks is the LOGIC the kernel was
 written from before it met a GPU: every pair exactly once, the ring never overwritten, at most 127 descriptors waiting.  The kernel itself
-is checked on the GPU (scripts/gpu_k34_ab.py, tests/test_gpu_segments.py)."""
+is checked on the GPU (tests/test_gpu_segments.py)."""
 import numpy as np
 rng = np.random.default_rng(1)
 TILE=4096; QSEG=1280; RING=128

@@ -4,9 +4,9 @@
 
     python scripts/k34_isa_mix.py [tag]      -> profiles/<tag>_k34_isa_mix.json   (needs hipcc; run in the build container)
 
-tag r03b (default): the level form of the first pass, compiled alone (-DK34_ONLY_FORM=0: the shipped kernel also holds the
-lane-major form behind a switch, whose blocks never run), counters from profiles/r03b_pmc_k34_sq.json; tag r03: the lane-major
-form (-DK34_ONLY_FORM=96) with profiles/r03_pmc_k34_sq.json — the mix behind profiles/r03_bench_c4_rows_line.json.
+The kernel is compiled as it ships: its first pass has one form, the level emission.  tag (default r03b) names the counters
+it is weighed with, profiles/<tag>_pmc_k34_sq.json.  (profiles/r03_k34_isa_mix.json, the lane-major form of rounds 2 and 3,
+was made by an earlier version of this script from a kernel that no longer exists.)
 
 Inputs
   * the device assembly of mimeo_amd/csrc/k34_fused.hip (hipcc -S --cuda-device-only, the Makefile's flags), first-pass
@@ -15,13 +15,13 @@ Inputs
     at 8 waves per SIMD, quoted as cycles at the nominal 2.4 GHz.  Two classes fall out of it: simple VOP2 integer ops and
     v_add_f32 (add / sub / and / or / xor / shifts / mov) at ~2.55 cycles, everything else (VOP3, compares, selects, max /
     min, 24-bit multiplies, popcounts, funnel shifts, DPP, SDWA, packed ops) at ~4.35;
-  * profiles/r03_pmc_k34_sq.json: SQ_INSTS_VALU per first-pass launch on a C4 unit (10 Mbp x 10 Mbp).
+  * profiles/<tag>_pmc_k34_sq.json: SQ_INSTS_VALU per first-pass launch on a C4 unit (10 Mbp x 10 Mbp).
 The kernel's work is two nested bodies: the PAIR ROUND (64 seed hits: descriptor read, 13 ds_bpermute + 3 ds_read_b128,
-the pre-filter, compaction) and the CHUNK VISIT (64 target entries against one query segment: 13 probes in LDS, prefix
-sum, descriptor emission).  Static instruction counts per body come from the basic blocks between the loop headers the
-compiler names; the dynamic weights are the launch's rounds (seed hits / 64 / lane utilisation of the rounds, measured
-by SQ_THREAD_CYCLES_VALU / SQ_INSTS_VALU) and visits (tiles x segments x chunks), and the model's total is checked
-against the measured SQ_INSTS_VALU.
+the pre-filter, compaction) and the CHUNK VISIT (64 target entries against one query segment: 13 probes in LDS, the
+level-by-level descriptor emission).  Static instruction counts per body come from the basic blocks between the loop
+headers the compiler names; the dynamic weights are the launch's rounds (seed hits / 64 / lane utilisation of the rounds,
+measured by SQ_THREAD_CYCLES_VALU / SQ_INSTS_VALU) and visits (tiles x segments x chunks), and the model's total is
+checked against the measured SQ_INSTS_VALU.
 """
 import collections
 import json
@@ -74,10 +74,9 @@ def classify(op):
 
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else 'r03b'
-    form = '96' if tag == 'r03' else '0'
     with tempfile.TemporaryDirectory() as td:
         asm = os.path.join(td, 'k34.s')
-        subprocess.check_call(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-w', '-S', '-DK34_ONLY_FORM=' + form,
+        subprocess.check_call(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-w', '-S',
                                '--cuda-device-only', '-o', asm, os.path.join(ROOT, 'mimeo_amd', 'csrc', 'k34_fused.hip')],
                               stderr=subprocess.DEVNULL)
         src = open(asm).read().split('\n')
@@ -144,28 +143,21 @@ def main():
     # partly empty; visits = 4096 tiles x 2 segments x ceil(2441 / 64) chunks
     hits = 7.78e7
     visits = 4096 * 2 * 39
-    rounds_full = hits / 64
     # straight-line share of a round actually executed: the filter block and the fetch always, the flush / emission side blocks rarely
     round_valu = {'valu_full': filt['valu_full'] + per_block[fetch]['valu_full'], 'valu_half': filt['valu_half'] + per_block[fetch]['valu_half']}
     round_all = {'valu_full': tot(rnd, 'valu_full'), 'valu_half': tot(rnd, 'valu_half')}
     visit_all = {'valu_full': tot(visit, 'valu_full'), 'valu_half': tot(visit, 'valu_half')}
-    if form == '96':
-        # lane-major form.  rounds: partial last rounds — about half a round per visit on top of the full ones; a visit executes its
-        # probe block once and the emission loop body ~3.4 times (non-empty probes per lane, worst lane of 64: ~9)
-        rounds = rounds_full + 0.5 * visits
-        model = rounds * (round_valu['valu_full'] + round_valu['valu_half']) + visits * (visit_all['valu_full'] + visit_all['valu_half']) * 1.6
-    else:
-        # level form.  The visit's last, partial round is a copy of the round among the visit's own blocks; the level loop body
-        # (~9 VALU) runs ~36 times in a visit of the segment's own half of the key space (12 probes x ~3 levels) and ~3 times in
-        # a visit of the other half: ~19.5 x 9 / 370 = +0.47 of the visit's static count
-        rounds = rounds_full
-        model = rounds * (round_valu['valu_full'] + round_valu['valu_half']) + visits * (visit_all['valu_full'] + visit_all['valu_half']) * 1.47
+    # The visit's last, partial round is a copy of the round among the visit's own blocks; the level loop body (~9 VALU) runs
+    # ~36 times in a visit of the segment's own half of the key space (12 probes x ~3 levels) and ~3 times in a visit of the
+    # other half: ~19.5 x 9 / 370 = +0.47 of the visit's static count
+    rounds = hits / 64
+    model = rounds * (round_valu['valu_full'] + round_valu['valu_half']) + visits * (visit_all['valu_full'] + visit_all['valu_half']) * 1.47
     share_round = rounds * (round_valu['valu_full'] + round_valu['valu_half']) / insts
     full_share = (rounds * round_valu['valu_full'] + (insts - rounds * (round_valu['valu_full'] + round_valu['valu_half'])) *
                   visit_all['valu_full'] / max(1, visit_all['valu_full'] + visit_all['valu_half'])) / insts
     c_mix = full_share * c_full + (1 - full_share) * c_half
     out = {
-        'what': 'opcode mix of k34_scan_extend<512,1280,false> (first pass, %s form compiled alone) from its gfx950 ISA, priced with profiles/r03_valu_rate.txt' % ('lane-major' if form == '96' else 'level'),
+        'what': 'opcode mix of k34_scan_extend<512,1280,false> (first pass, level form compiled alone) from its gfx950 ISA, priced with profiles/r03_valu_rate.txt',
         'issue_cycles_at_2.4GHz': {'full_rate_class': round(c_full, 3), 'half_rate_class': round(c_half, 3), 'ubench_rows': [n_full, n_half],
                                    'full_rate_ops': sorted(FULL_RATE)},
         'static': {'pair_round_blocks': rnd, 'prefilter_block': filt, 'chunk_visit_blocks': visit,

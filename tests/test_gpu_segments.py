@@ -6,7 +6,7 @@ and a 20 Mbp super-scaffold four.  The offsets clamped to a segment, the probes 
 that runs across a segment's chunks and the prefetch wrap from a segment's last target chunk to the next segment's first only
 show at those sizes.  These tests put exactly those shapes under (a) the C oracle, at sizes it finishes in seconds (its cost
 goes with Lt x Lq), and (b) the round-1 decomposition of the same stage (MIMEO_HEAVY=v1: stand-alone seed scan K3 + hit array
-+ K4 fast kernel) and the other forms of the first pass (MIMEO_K34_FORM), byte for byte, at C2 / C4 unit size; the packed
++ K4 fast kernel), byte for byte, at C2 / C4 unit size; the packed
 path's four-segment super-scaffolds are compared with the unit-per-pair path on the whole C2 job."""
 import hashlib
 
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 HCOLS = ['tstart', 'qstart', 'length', 'score', 'raw_score']
 ACOLS = ['tstart', 'tend', 'qstart', 'qend', 'score', 'id_n', 'id_d', 'qstrand']
-ENV = ('MIMEO_HEAVY', 'MIMEO_K4_VARIANT', 'MIMEO_PACK', 'MIMEO_BATCH_UNITS', 'MIMEO_K34_FORM')
+ENV = ('MIMEO_HEAVY', 'MIMEO_K4_VARIANT', 'MIMEO_PACK', 'MIMEO_BATCH_UNITS')
 
 
 @pytest.fixture(scope='module')
@@ -96,15 +96,13 @@ def test_fullsize_units_fused_equals_round1_decomposition(eng, monkeypatch, seed
     """BASELINE-sized units: K34 (default) against MIMEO_HEAVY=v1 — the stand-alone seed scan K3 writing the hit
     array and round 1's K4 fast kernel reading it: another enumeration of the hits (no segments, no frames, no
     descriptors), another filter, the same exact walks — HSPs byte for byte, both strands, a cross unit and a self
-    unit, and the same number of seed hits.  And the four forms of K34's first pass (MIMEO_K34_FORM): two-segment tiles cut
-    at the middle key with the level emission (a chunk of one half of the key space takes 12 probes or 1 instead of 13; a C2
-    tile is one segment and must not care), tiles cut by entry count with the level emission, and either cut with the prefix
-    sum + lane-major emission."""
+    unit, and the same number of seed hits.  A C4 tile is two segments, cut at the middle key when both halves fit (a chunk
+    of one half of the key space takes 12 probes or 1 instead of 13), else by entry count: the C4 unit runs both cuts; a C2
+    tile is one segment and must not care."""
     names, seqs = synth_genome(seed, 2 * L, 2, repeat_frac=0.05)
     g = eng.Genome(names, seqs)
     res = {}
-    for tag, env in (('fused', {}), ('v1', {'MIMEO_HEAVY': 'v1'}), ('level', {'MIMEO_K34_FORM': 'level'}), ('cut', {'MIMEO_K34_FORM': 'cut'}),
-                     ('half', {'MIMEO_K34_FORM': 'half'}), ('lane', {'MIMEO_K34_FORM': 'lane'})):
+    for tag, env in (('fused', {}), ('v1', {'MIMEO_HEAVY': 'v1'})):
         _clear(monkeypatch)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -115,10 +113,10 @@ def test_fullsize_units_fused_equals_round1_decomposition(eng, monkeypatch, seed
                 hits.append(eng.stats()['seed_hits'])
         res[tag] = (out, hits)
     _clear(monkeypatch)
-    assert res['fused'][1] == res['v1'][1] == res['level'][1] == res['cut'][1] == res['half'][1] == res['lane'][1]
+    assert res['fused'][1] == res['v1'][1]
     assert res['fused'][1][0] > 13 * float(L) * L / 4 ** 12
-    for a, *others in zip(*(res[k][0] for k in ('fused', 'v1', 'level', 'cut', 'half', 'lane'))):
-        assert a.size > 100 and all(a.tobytes() == o.tobytes() for o in others)
+    for a, b in zip(res['fused'][0], res['v1'][0]):
+        assert a.size > 100 and a.tobytes() == b.tobytes()
     g.close()
 
 
