@@ -48,10 +48,19 @@ enum {
 /* Strand selector == lastz --strand=plus|minus|both (wrappers.py:1031 passes both). */
 enum { MIMEO_STRAND_PLUS = 1, MIMEO_STRAND_MINUS = 2, MIMEO_STRAND_BOTH = 3 };
 
+/* Anchor rule of the gapped stage (mimeo_params.anchor_rule): which anchors are skipped.
+ *   MIMEO_ANCHOR_BOX  an anchor inside the (t, q) box of an earlier alignment of its (pair, strand)
+ *                     (alignment specification v1, rule 6; the default)
+ *   MIMEO_ANCHOR_PATH an anchor on a match/mismatch column of the path of an earlier alignment of its
+ *                     (pair, strand): lastz's documented --gapped rule.  lastz also bounds a new extension
+ *                     by earlier alignments; that part is not implemented. */
+enum { MIMEO_ANCHOR_BOX = 0, MIMEO_ANCHOR_PATH = 1 };
+
 /*
  * Alignment parameters == the lastz flags the reference passes
  * (wrappers.py:1025-1037 / 786-798 / 607-653) plus the LASTZ defaults they imply.
- * mimeo_params_default() fills the values in brackets.
+ * mimeo_params_default() fills the values in brackets.  anchor_rule selects the skip rule of
+ * the gapped stage (MIMEO_ANCHOR_*); any other value is MIMEO_ERR_ARG.
  */
 typedef struct mimeo_params {
     int32_t hspthresh;    /* --hspthresh [3000]; also the gapped threshold (lastz default)  */
@@ -64,7 +73,8 @@ typedef struct mimeo_params {
     int32_t chain;        /* --chain [1]                                                  */
     int32_t gapped;       /* --gapped [1]                                                 */
     int32_t strand;       /* --strand [MIMEO_STRAND_BOTH]                                 */
-    int32_t reserved[6];
+    int32_t anchor_rule;  /* gapped-stage skip rule [MIMEO_ANCHOR_BOX]                    */
+    int32_t reserved[5];
 } mimeo_params;
 
 /* One raw seed hit: 0-based starts of the 19-base seed window (12of19, lastz default seed). */

@@ -34,6 +34,11 @@ def add_common(parser, prog, gff_default, label, prefix, with_b):
     parser.add_argument('--loglevel', type=str, default='INFO', choices=['DEBUG', 'INFO', 'WARNING', 'ERROR', 'CRITICAL'],
                         help='Set the logging level.')
     parser.add_argument('--device', type=int, default=None, help='GPU index (default: LOCAL_RANK or 0).')
+    parser.add_argument('--anchorRule', type=str, default='box', choices=['box', 'path'],
+                        help='Which anchors the gapped stage skips. box (default): an anchor inside the box of an earlier '
+                             'alignment of its pair and strand. path: an anchor on a match/mismatch column of the path of an '
+                             'earlier alignment (lastz\'s --gapped rule); unlike lastz, a new extension is not bounded by '
+                             'earlier alignments. Ignored with --recycle when the alignment file exists.')
 
 
 def init_logging(level):

@@ -24,7 +24,12 @@ SYMBOLS = [
 
 class Params(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('hspthresh', 'xdrop', 'ydrop', 'gap_open', 'gap_extend', 'transitions',
-                                         'entropy', 'chain', 'gapped', 'strand')] + [('reserved', C.c_int32 * 6)]
+                                         'entropy', 'chain', 'gapped', 'strand', 'anchor_rule')] + \
+               [('reserved', C.c_int32 * 5)]
+
+
+ANCHOR_BOX, ANCHOR_PATH = 0, 1   # Params.anchor_rule (MIMEO_ANCHOR_*)
+ANCHOR_RULES = {'box': ANCHOR_BOX, 'path': ANCHOR_PATH}
 
 
 class Stats(C.Structure):

@@ -83,6 +83,7 @@ int mimeo_params_default(mimeo_params *p) {
     memset(p, 0, sizeof *p);
     p->hspthresh = 3000; p->xdrop = 910; p->ydrop = 9400; p->gap_open = 400; p->gap_extend = 30;
     p->transitions = 1; p->entropy = 1; p->chain = 1; p->gapped = 1; p->strand = MIMEO_STRAND_BOTH;
+    p->anchor_rule = MIMEO_ANCHOR_BOX;
     return MIMEO_OK;
 }
 
@@ -195,6 +196,10 @@ static int check_params(const mimeo_params *p) {
         return MIMEO_ERR_ARG;
     }
     if (!(p->strand & MIMEO_STRAND_BOTH)) { set_error("strand selects nothing"); return MIMEO_ERR_ARG; }
+    if (p->anchor_rule != MIMEO_ANCHOR_BOX && p->anchor_rule != MIMEO_ANCHOR_PATH) {
+        set_error("anchor_rule must be MIMEO_ANCHOR_BOX (0) or MIMEO_ANCHOR_PATH (1)");
+        return MIMEO_ERR_ARG;
+    }
     return 0;
 }
 

@@ -18,6 +18,10 @@
 //   * jobs of different anchors are independent, only the skip rule is ordered: each round takes
 //     the next <= nbatch unskipped anchors of every group (k6_pick), extends them all (k6_dp),
 //     then replays the skip rule in order over the batch (k6_resolve).
+//   * path rule (mimeo_params.anchor_rule = MIMEO_ANCHOR_PATH, opt-in): an anchor is skipped iff it is a diagonal step of
+//     the path of an earlier alignment.  After a round's DP kernels k6_trace re-runs the round's halves with a traceback,
+//     checks them against the first run and leaves each path as gap-free blocks; k6_pick / k6_resolve<true> test the
+//     blocks of the alignments whose box holds the anchor.  The box-rule kernels are unchanged.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -884,6 +888,50 @@ __device__ __forceinline__ bool in_boxes(const mimeo_alignment *aln, uint32_t n,
     return __ballot(inside) != 0;
 }
 
+// ---- path rule (MIMEO_ANCHOR_PATH) ------------------------------------------------------------------------------
+// The path of an alignment = its diagonal (match / mismatch) steps from both halves, kept as gap-free blocks (t, q, len)
+// sorted by t.  A half's diagonal steps have distinct t (each consumes one target base) and the left half lies below the
+// anchor's t, the right half at or above it, so one binary search per half decides whether (t, q) is on the path.
+struct PathBlock {
+    uint32_t t, q, len;
+};
+constexpr uint32_t PATH_UNTRACED = 0xFFFFFFFFu;  // pidx[slot].x of a half whose traceback did not fit the trace pool
+struct PathView {
+    const uint2 *pidx;       // per half slot (as HalfResult): first block in blk, block count
+    const PathBlock *blk;    // block arena of the call
+    uint32_t *accrank;       // per alignment slot hsp_begin + e: rank of its anchor (written by k6_resolve)
+};
+__device__ __forceinline__ bool on_half_path(const PathBlock *blk, uint32_t n, uint2 a) {
+    uint32_t lo = 0, hi = n;  // first block with t > a.x
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (blk[mid].t <= a.x) lo = mid + 1; else hi = mid;
+    }
+    if (!lo) return false;
+    const PathBlock b = blk[lo - 1];
+    return a.x - b.t < b.len && a.y >= b.q && a.y - b.q == a.x - b.t;
+}
+// is anchor a on the path of the alignment of the anchor of rank `rank` (group hsp_begin b0)?
+__device__ __forceinline__ bool on_path(const PathView &P, const uint2 *anchors, uint64_t b0, uint32_t rank, uint2 a) {
+    const uint2 an = anchors[b0 + rank];
+    const uint2 ix = P.pidx[2u * (b0 + rank) + (a.x >= an.x ? 1u : 0u)];
+    if (ix.x == PATH_UNTRACED) return false;
+    return on_half_path(P.blk + ix.x, ix.y, a);
+}
+// the skip test of the rule in force against the n accepted alignments aln[b0 ..]: the box is a prefilter of the path
+template <bool PATH>
+__device__ __forceinline__ bool skip_test(const mimeo_alignment *aln, uint32_t n, uint2 a, const PathView &P,
+                                          const uint2 *anchors, uint64_t b0) {
+    if (!PATH) return in_boxes(aln + b0, n, a);
+    bool on = false;
+    for (uint32_t e = threadIdx.x & 63u; e < n; e += 64u) {
+        const mimeo_alignment &o = aln[b0 + e];
+        if (a.x >= o.tstart && a.x < o.tend && a.y >= o.qstart && a.y < o.qend && on_path(P, anchors, b0, P.accrank[b0 + e], a))
+            on = true;
+    }
+    return __ballot(on) != 0;
+}
+
 // Anchor states.  The skip rule is ordered (an anchor is skipped iff it lies in the box of an ACCEPTED
 // anchor of lower rank), so anchors are finalised strictly in rank order by k6_resolve; what k6_pick
 // may choose freely is which unfinalised anchors get their DP in this round.  Fragments of one repeat
@@ -900,11 +948,12 @@ __device__ __forceinline__ bool anchors_near(uint2 a, uint2 b) {
     return dd <= NEAR_DIAG && dp <= NEAR_POS;
 }
 
-// one wave per group
+// one wave per group; PATH: the skip test is the path rule (P is unused otherwise)
+template <bool PATH>
 __global__ __launch_bounds__(64) void k6_pick(Group *__restrict__ groups, const uint2 *__restrict__ anchors,
                                               const mimeo_alignment *__restrict__ aln, uint32_t bmax,
                                               uint8_t *__restrict__ astate, uint8_t *__restrict__ adefer,
-                                              DpJob *__restrict__ jobs, unsigned int *__restrict__ njobs) {
+                                              DpJob *__restrict__ jobs, unsigned int *__restrict__ njobs, PathView P) {
     __shared__ uint32_t sb[MAX_BATCH];  // ranks scheduled in this round
     Group &G = groups[blockIdx.x];
     const uint64_t b0 = G.hsp_begin;
@@ -913,7 +962,7 @@ __global__ __launch_bounds__(64) void k6_pick(Group *__restrict__ groups, const 
     for (uint32_t r = first; r < G.nchain && nb < bmax && r - first < PICK_SCAN; r++) {
         if (astate[b0 + r] != A_NEW) continue;  // wave-uniform; states of earlier rounds only
         const uint2 a = anchors[b0 + r];
-        if (in_boxes(aln + b0, G.nacc, a)) {
+        if (skip_test<PATH>(aln, G.nacc, a, P, anchors, b0)) {
             if (lane == 0) astate[b0 + r] = A_SKIPPED;
             continue;
         }
@@ -1125,12 +1174,253 @@ __global__ __launch_bounds__(ANY_THREADS) void k6_dp_any(const Group *__restrict
     if (tid == 0) res[job.slot] = best;
 }
 
+// ---- traceback of a half extension (path rule) -------------------------------------------------------------------------
+// Re-runs one half's DP over rows 1 .. i* (row r depends only on the rows above it, so they are the rows of the first
+// run) with the recurrences, pruning and tie-breaks of k6_dp_any, storing one traceback byte per computed cell, checks the
+// re-run against its HalfResult (best score and cell; matches / mismatches along the walked path) and walks back from
+// the best cell into gap-free blocks.  Traceback bits and the walk are those of the study oracle (box_vs_path.c):
+//   TB_HD     H took D (strictly better than the diagonal)      TB_CI     C took I (strictly better than H)
+//   TB_DOPEN  D opened from C of the row above                  TB_IOPEN  I opened from H of the column to the left
+// One workgroup of 256 threads per half; the two DP rows (scores only: counts come from the walk) live in LDS when the
+// band bound fits TR_LDS_COLS, else in a ring in the job's slice of the trace pool.  Pool slice of a job (trace_layout):
+// traceback bytes (row r at (r - 1) * W, column j at j - row_lo[r]) | row_lo[1 .. i*] | block scratch | ring.
+enum : uint8_t { TB_HD = 1, TB_CI = 2, TB_DOPEN = 4, TB_IOPEN = 8 };
+constexpr int TR_THREADS = 256;
+constexpr uint32_t TR_LDS_COLS = 2048;
+enum : uint32_t { TR_NONE = 0, TR_DIAG = 1, TR_DP = 2, TR_UNTRACED = 3 };
+struct TraceJob {
+    unsigned long long off;  // byte offset of the job's slice in the pool
+    uint32_t W, R;           // columns per traceback row (bound of every row's band); ring columns (power of two)
+    uint32_t mode, cap;      // TR_*; block capacity of the scratch
+};
+struct TraceLayout { unsigned long long rowlo, blk, ring, total; };
+__host__ __device__ inline unsigned long long tr_align(unsigned long long x) { return (x + 255ull) & ~255ull; }
+__host__ __device__ inline TraceLayout trace_layout(uint32_t rows, uint32_t W, uint32_t R, uint32_t cap) {
+    TraceLayout L;
+    L.rowlo = tr_align((unsigned long long)rows * W);
+    L.blk = L.rowlo + tr_align(4ull * (rows + 1ull));
+    L.ring = L.blk + tr_align(12ull * cap);
+    L.total = L.ring + (R > TR_LDS_COLS ? tr_align(16ull * R) : 0ull);
+    return L;
+}
+// errors of the trace (ctr[1]): the re-run or the walk disagrees with the first run; ctr[2] = the half's slot
+enum : uint32_t { TRERR_DP = 1, TRERR_WALK = 2, TRERR_ROOM = 3 };
+
+__global__ __launch_bounds__(TR_THREADS) void k6_trace(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
+                                                       const TraceJob *__restrict__ tjobs, uint32_t k0,
+                                                       const HalfResult *__restrict__ res, uint8_t *__restrict__ pool,
+                                                       PathBlock *__restrict__ arena, unsigned long long arena_cap,
+                                                       uint2 *__restrict__ pidx, unsigned int *__restrict__ ctr,
+                                                       int32_t O, int32_t E, int32_t Y) {
+    __shared__ int32_t s_ring[4 * TR_LDS_COLS];
+    __shared__ Cell s_scan[TR_THREADS / 64];
+    __shared__ Best4 s_best[TR_THREADS / 64];
+    __shared__ uint32_t s_first[TR_THREADS / 64], s_last[TR_THREADS / 64];
+    __shared__ uint32_t s_nb, s_off, s_bad;
+    const uint32_t k = k0 + blockIdx.x;
+    const DpJob job = jobs[k];
+    const TraceJob J = tjobs[k];
+    const HalfResult hr = res[job.slot];
+    const Group &G = groups[job.group];
+    const StrandView &T = G.T, &Q = G.Q;
+    const uint32_t at = job.at, aq = job.aq;
+    const int dir = job.dir;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (J.mode != TR_DP) {
+        if (tid == 0) {
+            uint2 ix = make_uint2(0u, 0u);
+            if (J.mode == TR_UNTRACED) ix.x = PATH_UNTRACED;
+            if (J.mode == TR_DIAG) {   // identical-suffix shortcut: the diagonal of its length
+                const unsigned int o = atomicAdd(&ctr[0], 1u);
+                if (o >= arena_cap) { ctr[1] = TRERR_ROOM; ctr[2] = job.slot; }
+                else {
+                    const uint32_t n = hr.i;
+                    arena[o] = dir > 0 ? PathBlock{at, aq, n} : PathBlock{at - n, aq - n, n};
+                    ix = make_uint2(o, 1u);
+                }
+            }
+            pidx[job.slot] = ix;
+        }
+        return;
+    }
+    const uint32_t lenB = dir > 0 ? Q.len - aq : aq;
+    const uint32_t W = J.W, M = J.R - 1u, rows = hr.i;
+    const TraceLayout Lay = trace_layout(rows, W, J.R, J.cap);
+    uint8_t *tb = pool + J.off;
+    uint32_t *rowlo = (uint32_t *)(pool + J.off + Lay.rowlo);
+    PathBlock *scratch = (PathBlock *)(pool + J.off + Lay.blk);
+    int32_t *ring = J.R <= TR_LDS_COLS ? s_ring : (int32_t *)(pool + J.off + Lay.ring);
+    int32_t *cs[2] = {ring, ring + 2u * J.R}, *ds[2] = {ring + J.R, ring + 3u * J.R};
+    if (tid == 0) s_bad = 0;
+    int32_t best = 0;
+    uint32_t bi = 0, bj = 0;
+    long long sbase = 0;
+    uint32_t lo = 0, hi = 0;
+    if (Y >= O + E) hi = min(lenB, (uint32_t)((Y - O) / E));
+    const uint32_t ext = (uint32_t)((Y + 200) / E) + 2u;
+    for (uint32_t j = tid; j <= hi; j += TR_THREADS) { cs[0][j & M] = j ? -O - (int32_t)j * E : 0; ds[0][j & M] = NEG; }
+    __syncthreads();
+    bool bad = hi + 2u > M;
+    uint32_t par = 0;
+    for (uint32_t i = 1; i <= rows && !bad; i++, par ^= 1u) {
+        int32_t *Pc = cs[par], *Pd = ds[par], *Nc = cs[par ^ 1u], *Nd = ds[par ^ 1u];
+        const int32_t thr = best - Y;
+        const Base1 ab = base_at(T, dir > 0 ? (int32_t)(at + i - 1) : (int32_t)(at - i));
+        const uint32_t hx = min(lenB, hi + 1u + ext);
+        const uint32_t ncols = hx - lo + 1u;
+        if (ncols > W || ncols + 2u > M) { bad = true; break; }
+        uint8_t *trow = tb + (size_t)(i - 1u) * W - lo;  // indexed by column
+        if (tid == 0) rowlo[i] = lo;
+        const uint32_t chunk = (ncols + TR_THREADS - 1) / TR_THREADS;
+        const uint32_t j0 = lo + tid * chunk, j1 = min(hx + 1u, j0 + chunk);
+        // pass 1: D and H = max(diagonal, D)
+        Cell run{NEG, 0, 0};   // nm carries the column of the maximum
+        for (uint32_t j = j0; j < j1; j++) {
+            const bool in = j <= hi;
+            const int32_t cp = in ? Pc[j & M] : NEG, dp = in ? Pd[j & M] : NEG;
+            int32_t dd = NEG, g = NEG;
+            uint8_t bits = 0;
+            if (dp > NEGH) dd = dp - E;
+            if (cp > NEGH && cp - O - E > dd) { dd = cp - O - E; bits |= TB_DOPEN; }
+            if (j >= 1 && j - 1 >= lo && j - 1 <= hi) {
+                const int32_t pc = Pc[(j - 1) & M];
+                if (pc > NEGH) {
+                    const Base1 qb = base_at(Q, dir > 0 ? (int32_t)(aq + j - 1) : (int32_t)(aq - j));
+                    g = pc + sub_score(ab.lo ^ qb.lo, ab.hi ^ qb.hi, ab.lo ^ ab.hi, ab.nm | qb.nm);
+                }
+            }
+            Nd[j & M] = dd;
+            int32_t hh = g;  // diagonal preferred on ties
+            if (dd > g) { hh = dd; bits |= TB_HD; }
+            Nc[j & M] = hh;
+            trow[j] = bits;
+            const int32_t u = hh > NEGH ? hh + (int32_t)(j - lo) * E : NEG;
+            if (u > run.s) { run.s = u; run.nm = j; }
+        }
+        // pass 2: exclusive max-plus scan of the chunk aggregates (ties to the left: the column the insertion opened at)
+        const Cell winc = wave_incl_maxscan(run);
+        if (lane == 63) s_scan[wave] = winc;
+        __syncthreads();
+        Cell acc{NEG, 0, 0};
+        for (uint32_t w = 0; w < wave; w++) acc = cmax_left(acc, s_scan[w]);
+        acc = cmax_left(acc, dpp_cell<0x138, 0xf>(winc));
+        // pass 3: C = max(H, I), prune, row statistics
+        Best4 rb{NEG, 0xFFFFFFFFu, 0, 0};
+        uint32_t myfirst = 0xFFFFFFFFu, mylast = 0;
+        for (uint32_t j = j0; j < j1; j++) {
+            const int32_t hh = Nc[j & M];
+            const bool ilive = acc.s > NEGH;
+            const int32_t I = ilive ? acc.s - O - (int32_t)(j - lo) * E : NEG;
+            uint8_t bits = (ilive && acc.nm + 1u == j) ? TB_IOPEN : 0;   // I(j) opened from H(j - 1)
+            const int32_t u = hh > NEGH ? hh + (int32_t)(j - lo) * E : NEG;
+            if (u > acc.s) { acc.s = u; acc.nm = j; }
+            int32_t c = hh;  // H preferred over I on ties
+            if (I > c) { c = I; bits |= TB_CI; }
+            const bool alive = c >= thr && c > NEGH;
+            Nc[j & M] = alive ? c : NEG;
+            if (!alive) Nd[j & M] = NEG;
+            trow[j] |= bits;
+            if (alive) {
+                if (myfirst == 0xFFFFFFFFu) myfirst = j;
+                mylast = j;
+                if (c > rb.s) { rb.s = c; rb.j = j; }
+            }
+        }
+        uint32_t wf = myfirst, wl = (myfirst == 0xFFFFFFFFu) ? 0u : mylast + 1u;
+        for (int o = 32; o > 0; o >>= 1) { wf = min(wf, (uint32_t)__shfl_xor((int)wf, o)); wl = max(wl, (uint32_t)__shfl_xor((int)wl, o)); }
+        const Best4 wb4 = wave_best(rb);
+        if (lane == 0) { s_first[wave] = wf; s_last[wave] = wl; s_best[wave] = wb4; }
+        __syncthreads();
+        uint32_t first_alive = 0xFFFFFFFFu, last1 = 0;
+        Best4 tbest{NEG, 0xFFFFFFFFu, 0, 0};
+        for (int w = 0; w < TR_THREADS / 64; w++) {
+            first_alive = min(first_alive, s_first[w]);
+            last1 = max(last1, s_last[w]);
+            const Best4 o = s_best[w];
+            if (o.s > tbest.s || (o.s == tbest.s && o.j < tbest.j)) tbest = o;
+        }
+        __syncthreads();
+        if (first_alive == 0xFFFFFFFFu) { bad = true; break; }   // the first run went on to row i*
+        lo = first_alive;
+        hi = last1 - 1u;
+        if (tbest.s > best) { best = tbest.s; bi = i; bj = tbest.j; }
+        if (best > 2000000000) {   // k6_dp_any's rebase (scores of 64 bits, cells of 32)
+            const int32_t K = 1000000000;
+            for (uint32_t j = lo + tid; j <= hi; j += TR_THREADS) {
+                if (Nc[j & M] > NEGH) Nc[j & M] -= K;
+                if (Nd[j & M] > NEGH) Nd[j & M] -= K;
+            }
+            best -= K;
+            sbase += K;
+            __syncthreads();
+        }
+    }
+    if (tid == 0 && (bad || bi != hr.i || bj != hr.j || sbase + best != half_score(hr))) { ctr[1] = TRERR_DP; ctr[2] = job.slot; s_bad = 1; }
+    __syncthreads();
+    if (s_bad) { if (tid == 0) pidx[job.slot] = make_uint2(0u, 0u); return; }
+    // walk back from the best cell (one lane); states 0 = C, 1 = H, 2 = D, 3 = I
+    if (tid == 0) {
+        uint32_t i = hr.i, j = hr.j, nm = 0, nx = 0, nb = 0, st = 0, bt = 0, bq = 0, bl = 0, pt = 0;
+        bool ok = true;
+        unsigned long long guard = 3ull * ((unsigned long long)i + j) + 3ull;
+        while ((i || j) && ok) {
+            if (!guard--) { ok = false; break; }
+            if (i == 0) { j--; continue; }   // row 0: an insertion chain back to the origin
+            const uint32_t rl = rowlo[i];
+            if (j < rl || j - rl >= W) { ok = false; break; }
+            const uint8_t b = tb[(size_t)(i - 1u) * W + (j - rl)];
+            if (st == 0) st = (b & TB_CI) ? 3u : 1u;
+            else if (st == 1) {
+                if (b & TB_HD) st = 2;
+                else {
+                    const uint32_t t = dir > 0 ? at + i - 1u : at - i, q = dir > 0 ? aq + j - 1u : aq - j;
+                    const Base1 x = base_at(T, (int32_t)t), y = base_at(Q, (int32_t)q);
+                    if (!((x.lo ^ y.lo) | (x.hi ^ y.hi) | x.nm | y.nm)) nm++; else nx++;
+                    // the diagonal steps of a half come in t order (descending for dir > 0): extend the block or start one
+                    if (bl && (dir > 0 ? t + 1u == pt : t == pt + 1u) && (int32_t)(t - q) == (int32_t)(bt - bq)) {
+                        bl++;
+                        if (dir > 0) { bt = t; bq = q; }
+                    } else {
+                        if (bl) { if (nb >= J.cap) { ok = false; break; } scratch[nb++] = PathBlock{bt, bq, bl}; }
+                        bt = t; bq = q; bl = 1;
+                    }
+                    pt = t;
+                    i--; j--; st = 0;
+                }
+            } else if (st == 2) { st = (b & TB_DOPEN) ? 0u : 2u; i--; }
+            else { st = (b & TB_IOPEN) ? 1u : 3u; j--; }
+        }
+        if (ok && bl) { if (nb >= J.cap) ok = false; else scratch[nb++] = PathBlock{bt, bq, bl}; }
+        if (!ok || nm != hr.nm || nx != hr.nx) { ctr[1] = TRERR_WALK; ctr[2] = job.slot; nb = 0; ok = false; }
+        if (ok && dir > 0)   // sorted by t
+            for (uint32_t a = 0, z = nb ? nb - 1u : 0u; a < z; a++, z--) { const PathBlock t = scratch[a]; scratch[a] = scratch[z]; scratch[z] = t; }
+        unsigned int o = 0;
+        if (nb) {
+            o = atomicAdd(&ctr[0], nb);
+            if (o + (unsigned long long)nb > arena_cap) { ctr[1] = TRERR_ROOM; ctr[2] = job.slot; nb = 0; }
+        }
+        s_nb = nb; s_off = o;
+        pidx[job.slot] = make_uint2(nb ? o : 0u, nb);
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < s_nb; e += TR_THREADS) arena[s_off + e] = scratch[e];
+}
+
+// the HalfResults of a round's jobs, in job order (read back to plan the traceback slices)
+__global__ void k6_trace_gather(const DpJob *__restrict__ jobs, uint32_t n, const HalfResult *__restrict__ res,
+                                HalfResult *__restrict__ out) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) out[k] = res[jobs[k].slot];
+}
+
 // one wave per group: finalise anchors in rank order as far as DP results exist
 constexpr uint32_t RESOLVE_NEW = 256;  // boxes accepted per invocation that fit the LDS list
+template <bool PATH>
 __global__ __launch_bounds__(64) void k6_resolve(Group *__restrict__ groups, const uint2 *__restrict__ anchors,
                                                  const HalfResult *__restrict__ res, mimeo_alignment *__restrict__ aln,
-                                                 uint8_t *__restrict__ astate, unsigned int *__restrict__ remaining) {
+                                                 uint8_t *__restrict__ astate, unsigned int *__restrict__ remaining, PathView P) {
     __shared__ uint4 sbox[RESOLVE_NEW];  // boxes accepted in this invocation (tstart, tend, qstart, qend)
+    __shared__ uint32_t srank[PATH ? RESOLVE_NEW : 1];  // ... and the ranks of their anchors (path rule)
     Group &G = groups[blockIdx.x];
     const uint64_t b0 = G.hsp_begin;
     const uint32_t nacc0 = G.nacc;
@@ -1140,12 +1430,13 @@ __global__ __launch_bounds__(64) void k6_resolve(Group *__restrict__ groups, con
         if (st == A_SKIPPED || st == A_ACCEPTED) continue;
         if (nnew == RESOLVE_NEW) break;
         const uint2 a = anchors[b0 + r];
-        bool inside = in_boxes(aln + b0, nacc0, a);  // boxes of earlier invocations (visible in global memory)
+        bool inside = skip_test<PATH>(aln, nacc0, a, P, anchors, b0);  // alignments of earlier invocations (global memory)
         if (!inside) {
             bool in2 = false;
             for (uint32_t e = threadIdx.x; e < nnew; e += 64) {
                 uint4 o = sbox[e];
-                if (a.x >= o.x && a.x < o.y && a.y >= o.z && a.y < o.w) in2 = true;
+                if (a.x >= o.x && a.x < o.y && a.y >= o.z && a.y < o.w && (!PATH || on_path(P, anchors, b0, srank[PATH ? e : 0], a)))
+                    in2 = true;
             }
             inside = __ballot(in2) != 0;
         }
@@ -1157,6 +1448,8 @@ __global__ __launch_bounds__(64) void k6_resolve(Group *__restrict__ groups, con
         const uint32_t slot = 2u * (uint32_t)(b0 + r);
         HalfResult L = res[slot], R = res[slot + 1];
         overflow |= L.overflow | R.overflow;
+        // path rule: a half without a traceback (larger than the trace pool) fails the group like a band beyond the limit
+        if (PATH && (P.pidx[slot].x == PATH_UNTRACED || P.pidx[slot + 1].x == PATH_UNTRACED)) overflow = 1;
         if (threadIdx.x == 0) {
             mimeo_alignment m;
             m.tid = G.tid; m.qid = G.qid; m.qstrand = G.minus; m.reserved = 0;
@@ -1166,6 +1459,7 @@ __global__ __launch_bounds__(64) void k6_resolve(Group *__restrict__ groups, con
             m.id_d = L.nm + R.nm + L.nx + R.nx;
             aln[b0 + nacc0 + nnew] = m;
             sbox[nnew] = make_uint4(m.tstart, m.tend, m.qstart, m.qend);
+            if (PATH) { srank[PATH ? nnew : 0] = r; P.accrank[b0 + nacc0 + nnew] = r; }
             astate[b0 + r] = A_ACCEPTED;
         }
         nnew++;
@@ -1261,6 +1555,108 @@ void dense_alignments_device(Group *d_groups, uint32_t ngroups, const mimeo_alig
 }
 
 static DeviceBuf g_anchors, g_packed, g_jobs, g_res, g_cnt, g_astate, g_ovf_list, g_any;
+// path rule: per half slot (first block, count), per alignment slot the anchor's rank, the block arena, the trace pool
+static DeviceBuf g_pidx, g_accrank, g_arena, g_pool, g_tjobs, g_tres, g_tctr;
+
+// bytes of traceback the path rule may hold at once: a share of the free device memory (like the queue arenas of K4);
+// MIMEO_K6_TRACE_POOL_MB sets it (tests: force slices, or a pool too small for one half)
+static int trace_pool_budget(uint64_t *budget) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    *budget = std::min<uint64_t>(((uint64_t)free_b + g_pool.cap) / 4, 16ull << 30);
+    if (getenv("MIMEO_K6_TRACE_POOL_MB")) *budget = (uint64_t)atol(getenv("MIMEO_K6_TRACE_POOL_MB")) << 20;
+    return 0;
+}
+
+// the block arena grows with its contents (block offsets stay valid)
+static int arena_reserve(uint64_t blocks, uint64_t used) {
+    const size_t bytes = (size_t)blocks * sizeof(PathBlock);
+    if (bytes <= g_arena.cap) return 0;
+    DeviceBuf nb;
+    int rc = nb.reserve(std::max(bytes, 2 * g_arena.cap));
+    if (rc) return rc;
+    if (used) HIP_TRY(hipMemcpyAsync(nb.p, g_arena.p, (size_t)used * sizeof(PathBlock), hipMemcpyDeviceToDevice, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    g_arena.release();
+    g_arena = nb;
+    return 0;
+}
+
+// path rule, after the DP kernels of a round: the traceback of every half of the round's h0 jobs, in slices of jobs whose
+// tracebacks fit the pool together.  A half whose traceback alone exceeds the pool gets no path (PATH_UNTRACED): k6_resolve
+// fails its group if the anchor is accepted, as for a band beyond the DP limit.
+static int trace_round(Group *d_groups, uint32_t h0, const mimeo_params *p, uint64_t budget, uint64_t *arena_used, float *ms,
+                       uint32_t *slices, uint64_t *largest) {
+    hipStream_t st = stream();
+    int rc;
+    if ((rc = g_tres.reserve((size_t)h0 * sizeof(HalfResult)))) return rc;
+    hipLaunchKernelGGL(k6_trace_gather, dim3((h0 + 255) / 256), dim3(256), 0, st, (const DpJob *)g_jobs.p, h0, (const HalfResult *)g_res.p,
+                       (HalfResult *)g_tres.p);
+    std::vector<HalfResult> hr(h0);
+    HIP_TRY(hipMemcpyAsync(hr.data(), g_tres.p, (size_t)h0 * sizeof(HalfResult), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int32_t O = p->gap_open, E = p->gap_extend, Y = p->ydrop;
+    const uint32_t ext = (uint32_t)((Y + 200) / E) + 2u, hi0 = Y >= O + E ? (uint32_t)((Y - O) / E) : 0u;
+    std::vector<TraceJob> tj(h0);
+    std::vector<uint32_t> cut{0};   // slice boundaries
+    uint64_t fill = 0, need_max = 0, blocks = 0;
+    for (uint32_t k = 0; k < h0; k++) {
+        const HalfResult &r = hr[k];
+        TraceJob J{0, 0, 0, TR_NONE, 0};
+        if (!r.overflow && r.i) {
+            if (r.rows == 0) { J.mode = TR_DIAG; blocks += 1; }
+            else {
+                J.W = std::max(r.maxcols, hi0 + 1u) + ext + 2u;
+                J.R = 1u;
+                while (J.R < J.W + 2u) J.R <<= 1;
+                J.cap = std::min(r.i, r.j) + 1u;
+                const uint64_t need = trace_layout(r.i, J.W, J.R, J.cap).total;
+                *largest = std::max(*largest, need);
+                if (need > budget) J.mode = TR_UNTRACED;
+                else {
+                    J.mode = TR_DP;
+                    blocks += J.cap;
+                    if (fill + need > budget) { cut.push_back(k); fill = 0; }
+                    J.off = fill;
+                    fill += need;
+                    need_max = std::max(need_max, fill);
+                }
+            }
+        }
+        tj[k] = J;
+    }
+    cut.push_back(h0);
+    if ((rc = g_tjobs.reserve((size_t)h0 * sizeof(TraceJob)))) return rc;
+    HIP_TRY(hipMemcpyAsync(g_tjobs.p, tj.data(), (size_t)h0 * sizeof(TraceJob), hipMemcpyHostToDevice, st));
+    if (need_max && (rc = g_pool.reserve(need_max))) return rc;
+    if ((rc = arena_reserve(*arena_used + blocks + 1, *arena_used))) return rc;
+    static hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (!e0) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
+    HIP_TRY(hipEventRecord(e0, st));
+    for (size_t c = 0; c + 1 < cut.size(); c++)
+        if (cut[c + 1] > cut[c] && ++*slices)
+            hipLaunchKernelGGL(k6_trace, dim3(cut[c + 1] - cut[c]), dim3(TR_THREADS), 0, st, (const Group *)d_groups,
+                               (const DpJob *)g_jobs.p, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
+                               (uint8_t *)g_pool.p, (PathBlock *)g_arena.p, (unsigned long long)(g_arena.cap / sizeof(PathBlock)),
+                               (uint2 *)g_pidx.p, (unsigned int *)g_tctr.p, O, E, Y);
+    HIP_TRY(hipEventRecord(e1, st));
+    unsigned int c3[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(c3, g_tctr.p, 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+    *ms += t;
+    if (c3[1]) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "internal: K6 traceback of half slot %u %s", c3[2],
+                 c3[1] == TRERR_DP ? "disagrees with its DP result (score or end cell)"
+                 : c3[1] == TRERR_WALK ? "disagrees with its DP result (matches / mismatches along the path)" : "outgrew the block arena");
+        set_error(msg);
+        return MIMEO_ERR_ARG;
+    }
+    *arena_used = c3[0];
+    return 0;
+}
 
 int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, const uint32_t *d_order,
                   uint64_t nhsps, const mimeo_params *p, mimeo_alignment *d_aln) {
@@ -1293,12 +1689,33 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
                            d_sorted, d_order, (unsigned long long *)g_packed.p);
         hipLaunchKernelGGL(k6_anchor_final, dim3(ngroups), dim3(256), 0, st, (const Group *)d_groups, d_sorted, d_order,
                            (const unsigned long long *)g_packed.p, (uint2 *)g_anchors.p);
+        const bool path = p->anchor_rule == MIMEO_ANCHOR_PATH;
+        uint64_t pool_budget = 0, arena_used = 0;
+        float ms_trace = 0;
+        uint32_t trace_slices = 0, rounds = 0;
+        uint64_t largest = 0;   // largest traceback of one half (bytes)
+        PathView pv{nullptr, nullptr, nullptr};
+        if (path) {
+            if ((rc = g_pidx.reserve((size_t)nhsps * 2 * sizeof(uint2)))) return rc;
+            if ((rc = g_accrank.reserve((size_t)nhsps * 4))) return rc;
+            if ((rc = g_tctr.reserve(16))) return rc;
+            if ((rc = arena_reserve(1024, 0))) return rc;
+            HIP_TRY(hipMemsetAsync(g_tctr.p, 0, 16, st));
+            if ((rc = trace_pool_budget(&pool_budget))) return rc;
+            pv = PathView{(const uint2 *)g_pidx.p, nullptr, (uint32_t *)g_accrank.p};
+        }
         for (;;) {
             HIP_TRY(hipMemsetAsync(g_cnt.p, 0, 16, st));
             unsigned int *njobs = (unsigned int *)g_cnt.p, *remaining = njobs + 1, *novf = njobs + 2;
-            hipLaunchKernelGGL(k6_pick, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                               (const mimeo_alignment *)d_aln, bmax, (uint8_t *)g_astate.p, (uint8_t *)g_astate.p + nhsps,
-                               (DpJob *)g_jobs.p, njobs);
+            pv.blk = (const PathBlock *)g_arena.p;   // the arena may have grown in the last round
+            if (path)
+                hipLaunchKernelGGL(k6_pick<true>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
+                                   (const mimeo_alignment *)d_aln, bmax, (uint8_t *)g_astate.p, (uint8_t *)g_astate.p + nhsps,
+                                   (DpJob *)g_jobs.p, njobs, pv);
+            else
+                hipLaunchKernelGGL(k6_pick<false>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
+                                   (const mimeo_alignment *)d_aln, bmax, (uint8_t *)g_astate.p, (uint8_t *)g_astate.p + nhsps,
+                                   (DpJob *)g_jobs.p, njobs, pv);
             unsigned int h[2] = {0, 0};
             HIP_TRY(hipMemcpyAsync(h, g_cnt.p, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
@@ -1362,12 +1779,24 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
                 for (auto &r : hr)
                     if (!r.rows && shown < 8) { fprintf(stderr, "  [k6] zero-row job: score %d i %u j %u nm %u nx %u ovf %u\n", r.score, r.i, r.j, r.nm, r.nx, r.overflow); shown++; }
             }
-            hipLaunchKernelGGL(k6_resolve, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                               (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining);
+            if (path && h[0]) {
+                rounds++;
+                if ((rc = trace_round(d_groups, h[0], p, pool_budget, &arena_used, &ms_trace, &trace_slices, &largest))) return rc;
+                pv.blk = (const PathBlock *)g_arena.p;
+            }
+            if (path)
+                hipLaunchKernelGGL(k6_resolve<true>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
+                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv);
+            else
+                hipLaunchKernelGGL(k6_resolve<false>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
+                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv);
             HIP_TRY(hipMemcpyAsync(h, g_cnt.p, 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             if (!h[1]) break;
         }
+        if (path && k6_stats)
+            fprintf(stderr, "[k6] path rule: traceback %.3f ms, rounds %u slices %u, %llu path blocks, pool %.1f MB, largest half %.3f MB\n", ms_trace,
+                    rounds, trace_slices, (unsigned long long)arena_used, g_pool.cap / 1048576.0, largest / 1048576.0);
     }
     hipLaunchKernelGGL(k6_finish, dim3((ngroups + 63) / 64), dim3(64), 0, st, d_groups, ngroups, d_aln, p->hspthresh);
     HIP_TRY(hipGetLastError());

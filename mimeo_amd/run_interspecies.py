@@ -32,7 +32,7 @@ def main(argv=None):
     logging.info('Running alignments...')
     workflow.self_repeats(A, pairs, outtab, gffout, minIdt=args.minIdt, minLen=args.minLen, hspthresh=3000,
                           minCov=args.minCov, reuseTab=args.recycle, label=args.label, prefix=args.prefix, dist=dist,
-                          source='mimeo', B=B)
+                          source='mimeo', B=B, anchor_rule=args.anchorRule)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

@@ -37,7 +37,7 @@ def main(argv=None):
         logging.error('No files to align. Check --adir and --bdir contain at least one fasta each.')
         sys.exit(1)
     workflow.map_hits(A, B, pairs, outtab, minIdt=args.minIdt, minLen=args.minLen, hspthresh=args.hspthresh,
-                      reuseTab=args.recycle, dist=dist)
+                      reuseTab=args.recycle, dist=dist, anchor_rule=args.anchorRule)
     if dist.rank == 0:
         logging.info('Importing alignments from %s' % outtab)
         rows = formats.parse_tab(outtab)

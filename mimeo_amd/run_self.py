@@ -33,7 +33,8 @@ def main(argv=None):
     logging.info('Running alignments...')
     workflow.self_repeats(A, pairs, outtab, gffout, minIdt=args.minIdt, minLen=args.minLen, hspthresh=args.hspthresh,
                           minCov=args.minCov, intraCov=args.intraCov, splitSelf=args.strictSelf, reuseTab=args.recycle,
-                          label=args.label, prefix=args.prefix, dist=dist)
+                          label=args.label, prefix=args.prefix, dist=dist,
+                          anchor_rule=args.anchorRule)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

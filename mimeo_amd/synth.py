@@ -90,6 +90,39 @@ def make_families(rng, families=40, cons_len=(300, 6000)):
             for _ in range(families)]
 
 
+def add_tandem_arrays(seed, arrs, per_scaffold):
+    """Tandem arrays written over the scaffolds of synth_genome (new arrays; the input is not changed): `per_scaffold` arrays
+    per scaffold, each 8-30 diverged copies (mismatch rate U[0, 0.12]; 30 % of the copies gain or lose 1-20 bases at the end)
+    of one of three 150-900 bp units shared by every scaffold.  Chained HSPs on neighbouring diagonals inside one alignment
+    box are where the box and path anchor rules part; scripts/box_vs_path.py measures it on these genomes."""
+    rng = np.random.default_rng(seed + 7)
+    units = [rng.integers(0, 4, size=int(rng.integers(150, 900)), dtype=np.uint8) for _ in range(3)]
+    acgt = np.frombuffer(b'ACGT', np.uint8)
+    arrs = [a.copy() for a in arrs]
+    for a in arrs:
+        for _ in range(per_scaffold):
+            u = units[int(rng.integers(0, 3))]
+            copies = []
+            for _c in range(int(rng.integers(8, 31))):
+                c = u.copy()
+                m = rng.random(c.size) < rng.random() * 0.12
+                c[m] = (c[m] + rng.integers(1, 4, size=int(m.sum()), dtype=np.uint8)) & 3
+                if rng.random() < 0.3:   # an indel of 1-20 bases between copies
+                    c = np.concatenate([c, rng.integers(0, 4, size=int(rng.integers(1, 21)), dtype=np.uint8)]) if rng.random() < 0.5 else c[:-int(rng.integers(1, 21))]
+                copies.append(c)
+            arr = acgt[np.concatenate(copies)]
+            if arr.size < a.size // 2:
+                pos = int(rng.integers(0, a.size - arr.size))
+                a[pos:pos + arr.size] = arr
+    return arrs
+
+
+def tandem_genome(seed, nscaf, scaf_bp, per_scaffold=3, repeat_frac=0.05, families=40):
+    """synth_genome(seed, nscaf * scaf_bp, nscaf, ...) with add_tandem_arrays on top: (names, list of uint8 ASCII arrays)"""
+    names, arrs = synth_genome(seed, nscaf * scaf_bp, nscaf, repeat_frac=repeat_frac, families=families)
+    return names, add_tandem_arrays(seed, arrs, per_scaffold)
+
+
 def write_fasta(path, names, seqs, width=60):
     with open(path, 'wb') as f:
         for n, s in zip(names, seqs):

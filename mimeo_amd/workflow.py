@@ -24,6 +24,15 @@ def all_pairs(n_a, n_b=None):
     return [(a, b) for a in range(n_a) for b in range(n_b)]
 
 
+def anchor_rule_code(rule):
+    """'box' / 'path' (CLI --anchorRule) or the number itself -> mimeo_params.anchor_rule"""
+    if isinstance(rule, str):
+        if rule not in engine._ffi.ANCHOR_RULES:
+            raise ValueError('anchor rule must be one of %s, not %r' % (sorted(engine._ffi.ANCHOR_RULES), rule))
+        return engine._ffi.ANCHOR_RULES[rule]
+    return int(rule)
+
+
 PACK_MEMBER_BP = 6 << 20   # the engine packs scaffolds of up to this size into super-scaffolds when there are at least ...
 PACK_MIN = 8               # ... this many of them (mimeo_hip.h, mimeo_align_pairs)
 
@@ -100,13 +109,14 @@ def collapse_to_gff(tab_path, names, lengths, min_cov, min_len, source, label, p
 
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
-                 B=None):
-    """`mimeo self` (and, with B and source='mimeo', `mimeo x`)."""
+                 B=None, anchor_rule='box'):
+    """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  anchor_rule: the gapped stage's skip rule, 'box' or
+    'path' (or its _ffi.ANCHOR_* number; mimeo_hip.h MIMEO_ANCHOR_*)."""
     dist = dist or Dist()
     outtab_intra = outtab + '_intra.tab'
     kept = None
     if not reuseTab or not os.path.isfile(outtab):
-        params = engine.default_params(hspthresh=hspthresh)
+        params = engine.default_params(hspthresh=hspthresh, anchor_rule=anchor_rule_code(anchor_rule))
         blocks, _, kept = align_blocks(A, B, pairs, params, minLen, minIdt, dist)
         if len(set(pairs)) != len(pairs):
             kept = None   # a pair listed twice is written twice (the reference would run it twice): read the file back instead
@@ -139,11 +149,11 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     return lines
 
 
-def map_hits(A, B, pairs, outtab, minIdt=95, minLen=100, hspthresh=3000, reuseTab=False, dist=None):
-    """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse."""
+def map_hits(A, B, pairs, outtab, minIdt=95, minLen=100, hspthresh=3000, reuseTab=False, dist=None, anchor_rule='box'):
+    """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse.  anchor_rule as self_repeats."""
     dist = dist or Dist()
     if not reuseTab or not os.path.isfile(outtab):
-        params = engine.default_params(hspthresh=hspthresh)
+        params = engine.default_params(hspthresh=hspthresh, anchor_rule=anchor_rule_code(anchor_rule))
         blocks, _, _ = align_blocks(A, B, pairs, params, minLen, minIdt, dist)
         if dist.rank == 0:
             write_tab(outtab, pairs, blocks)

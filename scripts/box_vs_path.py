@@ -23,7 +23,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from mimeo_amd.synth import synth_genome  # noqa: E402
+from mimeo_amd.synth import add_tandem_arrays, synth_genome  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from oracle import pipeline as P  # noqa: E402
 
@@ -99,25 +99,7 @@ def main():
     names, arrs = synth_genome(seed, S * L, S, repeat_frac=frac, families=fams)
     ntand = int(sys.argv[6]) if len(sys.argv) > 6 else 0
     if ntand:
-        rng = np.random.default_rng(seed + 7)
-        units = [rng.integers(0, 4, size=int(rng.integers(150, 900)), dtype=np.uint8) for _ in range(3)]
-        acgt = np.frombuffer(b'ACGT', np.uint8)
-        arrs = [a.copy() for a in arrs]
-        for a in arrs:
-            for _ in range(ntand):
-                u = units[int(rng.integers(0, 3))]
-                copies = []
-                for _c in range(int(rng.integers(8, 31))):
-                    c = u.copy()
-                    m = rng.random(c.size) < rng.random() * 0.12
-                    c[m] = (c[m] + rng.integers(1, 4, size=int(m.sum()), dtype=np.uint8)) & 3
-                    if rng.random() < 0.3:   # an indel of 1-20 bases between copies
-                        c = np.concatenate([c, rng.integers(0, 4, size=int(rng.integers(1, 21)), dtype=np.uint8)]) if rng.random() < 0.5 else c[:-int(rng.integers(1, 21))]
-                    copies.append(c)
-                arr = acgt[np.concatenate(copies)]
-                if arr.size < a.size // 2:
-                    pos = int(rng.integers(0, a.size - arr.size))
-                    a[pos:pos + arr.size] = arr
+        arrs = add_tandem_arrays(seed, arrs, ntand)
     seqs = [a.tobytes() for a in arrs]
     lib()
     pairs = [(t, q) for t in range(S) for q in range(S)]
