@@ -206,6 +206,10 @@ struct ExtBatch {
     // queue sizing: largest excess over the random-sequence shares seen so far, per queue (followers, walks beyond the frame,
     // long walks, candidates, walk queue): microsatellites flood the follower queue alone (C5: half of all hits)
     double boost_f = 1.0, boost_m = 1.0, boost_l = 1.0, boost_c = 1.0, boost_w = 1.0;
+    // ... within one API call: every call starts from the random-sequence shares.  Boosts learned on one input would size
+    // the queues of every later call on any other (a tandem-array job of 1e6 expected hits left boosts of ~100-300; the C4
+    // row after it was cut into 125 batches instead of one, and a C2 call after that asked for 190 GiB of queues)
+    void new_call() { boost_f = boost_m = boost_l = boost_c = boost_w = 1.0; }
     // run = start (the heavy phase of the batch is enqueued on the calling thread's stream, nothing is waited for) + finish
     // (tails on the calling thread's stream at that time, which may be another one: two host round trips; a batch whose queues
     // overflowed is repeated there with room).  The pipeline starts the next batch before it finishes this one.

@@ -144,6 +144,7 @@ void release_pipeline_buffers() {
 int ungapped_units(const std::vector<UnitWork> &work, const mimeo_params *p, std::vector<std::vector<mimeo_hsp>> *per_unit,
                    ExtStats *st) {
     uint64_t nh = 0;
+    g_ext.new_call();
     int rc = g_ext.run(work, p, &nh, st);
     if (rc) return rc;
     per_unit->assign(work.size(), std::vector<mimeo_hsp>());
@@ -413,6 +414,7 @@ int align_units_impl(const mimeo_genome *A, const mimeo_genome *B, const uint32_
     auto t0 = std::chrono::steady_clock::now();
     memset(&g_stats, 0, sizeof g_stats);
     g_failed.clear();
+    g_ext.new_call();
     const Switches sw;
     const mimeo_genome *QG = B ? B : A;
     uint64_t max_t = 1, max_q = 1;

@@ -1,8 +1,10 @@
 """BASELINE-sized units (C2 scaffolds: 5 Mbp x 5 Mbp, seed 50; C4 scaffolds: 10 Mbp x 10 Mbp, seed 1000) and the
-whole C2 job (10 scaffolds, 100 ordered pairs) checked through size-independent properties,
-because the CPU oracle needs minutes at this size: symmetry of the seed relation, validity of a
-sample of hits against a numpy restatement of the seed rule, HSP scores recomputed on the host,
-run-to-run determinism, and self-consistency of the full alignment stage."""
+whole C2 job (10 scaffolds, 100 ordered pairs) checked through size-independent properties:
+symmetry of the seed relation, validity of a sample of hits against a numpy restatement of the seed
+rule, HSP scores recomputed on the host, run-to-run determinism, and self-consistency of the full
+alignment stage.  The CPU oracle needs a minute or two per 10 Mbp unit and strand, so it sees C4 units
+in test_gpu_c4_row.py: a fixed sample of the bench's own row 0, alignment records unit by unit, with
+the whole row also checked byte for byte against the round-1 decomposition."""
 import numpy as np
 import pytest
 
