@@ -200,7 +200,8 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     // first pass: grid (tiles, units); split pass: grid (HEAVY_MAX x units, target shares, query shares)
     uint32_t ai = HEAVY ? 0u : blockIdx.y;
-    FusedUnit U = A.units[ai];   // by value: wave-uniform registers, not a reload through the pointer at every use (split pass: set per part)
+    GFusedUnit U = A.units[ai];   // by value: wave-uniform registers, not a reload through the pointer at every use (split pass: set per part);
+                                  // its pointers come out of a table: held in global address space (device_util.h)
     // split pass: my part of the tile = target chunk groups p, p + Pt, ... and the query entries [qa, qb)
     uint32_t part_p = 0, part_pt = 1, part_qa = 0, part_qb = 0xFFFFFFFFu, part_no = 0;
     uint32_t *sD = sD_all + wv * DQ;
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
 
     // everything below returns for the whole workgroup at once (the conditions are uniform)
     auto do_tile = [&](const uint32_t tile) {
-        const uint32_t *toff = U.T.off + (size_t)tile * TILE_WORDS, *qoff = U.Q.off + (size_t)tile * TILE_WORDS;
+        const gptr<uint32_t> toff = U.T.off + (size_t)tile * TILE_WORDS, qoff = U.Q.off + (size_t)tile * TILE_WORDS;
         const uint32_t t0 = toff[0], nT = toff[TILE_WORDS] - t0;
         const uint32_t q0 = qoff[0], nQ = qoff[TILE_WORDS] - q0;
         if (!nT || !nQ) return;   // tile_hits is zeroed per batch
@@ -239,9 +240,9 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
             // tile — the seed_hits statistic — is the sum of the pairs its chunk visits enumerate (below).
             uint32_t *sT = reinterpret_cast<uint32_t *>(sQF), *sQ32 = sT + TILE_WORDS + 4;
             {
-                const uint4 *s0 = reinterpret_cast<const uint4 *>(toff), *s1 = reinterpret_cast<const uint4 *>(qoff);
+                const gptr<uint4> s0 = toff.as<uint4>(), s1 = qoff.as<uint4>();
                 uint4 *d0 = reinterpret_cast<uint4 *>(sT), *d1 = reinterpret_cast<uint4 *>(sQ32);
-                for (uint32_t k = threadIdx.x; k < TILE_WORDS / 4; k += THREADS) { d0[k] = s0[k]; d1[k] = s1[k]; }
+                for (uint32_t k = threadIdx.x; k < TILE_WORDS / 4; k += THREADS) { const uint4 a = s0[k], b = s1[k]; d0[k] = a; d1[k] = b; }
                 if (threadIdx.x == 0) { sT[TILE_WORDS] = t0 + nT; sQ32[TILE_WORDS] = q0 + nQ; *s_total = 0ull; }
             }
             __syncthreads();
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
             mid = (uint32_t)__builtin_amdgcn_readfirstlane((int)((reinterpret_cast<const uint32_t *>(sQF) + TILE_WORDS + 4)[TILE_WORDS / 2] - q0));
             aligned = mid <= QSEG && nQ - mid <= QSEG;   // (then 0 < mid < nQ: both segments hold entries)
         }
-        const uint4 *tF0 = U.T.fr + t0, *tF1 = tF0 + U.T.fr_stride, *tF2 = tF1 + U.T.fr_stride;
+        const gptr<uint4> tF0 = U.T.fr + t0, tF1 = tF0 + U.T.fr_stride, tF2 = tF1 + U.T.fr_stride;
         const uint32_t nchunks = (nT + TCH - 1) / TCH;
         // chunks of this workgroup: every one (first pass), or those of my share of the tile (split pass)
         const uint32_t ch_first = (HEAVY ? part_p * WAVES : 0u) + wv, ch_step = (HEAVY ? part_pt : 1u) * WAVES;
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
                 // interior members of runs of consecutive seed hits leave no record: out, before the filter (a microsatellite
                 // tile is nearly all of them: whole rounds skip the filter)
                 bool inner = false;
-                if (valid && ((tpf >> 31) | qflag) == 0 && U.Tv.svt == nullptr && run_interior(ta, tb, tc, qa, qb, qc, A.transitions)) {
+                if (valid && ((tpf >> 31) | qflag) == 0 && !U.Tv.svt && run_interior(ta, tb, tc, qa, qb, qc, A.transitions)) {
                     const uint32_t tp = tpf & POS_MASK;
                     inner = tp >= 2u && tp + 1u + SEED_LEN <= U.Tv.len;   // (the query's ends: bit 1 of its flag)
                 }
@@ -359,13 +360,17 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
                 if (k <= TILE_WORDS) sQ[k] = (qoff_t)(min(max(ro[i], qs), qe) - qs);
             }
             {
-                const uint4 *s0 = U.Q.fr + q0 + qs, *s1 = s0 + U.Q.fr_stride, *s2 = s1 + U.Q.fr_stride;
+                const gptr<uint4> s0 = U.Q.fr + q0 + qs, s1 = s0 + U.Q.fr_stride, s2 = s1 + U.Q.fr_stride;
+                const gptr<uint32_t> sp = U.Q.pos + q0 + qs;
+                // an entry's four loads are issued together, the LDS writes follow as the data arrives (counted vmcnt waits).  (Two
+                // entries per thread and trip, 8 loads in flight, measured no faster on a C4 row and cost 13 VGPRs; three spill.)
                 for (uint32_t i = threadIdx.x; i < qn; i += THREADS) {
-                    sQF[i] = s0[i];
-                    sQF[QSEG + i] = s1[i];
-                    sQF[2 * QSEG + i] = s2[i];
+                    const uint4 a = s0[i], b = s1[i], c = s2[i];
+                    const uint32_t pq = sp[i], pp = pq & POS_MASK;
+                    sQF[i] = a;
+                    sQF[QSEG + i] = b;
+                    sQF[2 * QSEG + i] = c;
                     // bit 0: N in the frame; bit 1: too close to an end of the scaffold for the run test's three seed windows
-                    const uint32_t pq = U.Q.pos[q0 + qs + i], pp = pq & POS_MASK;
                     sQN[i] = (uint8_t)((pq >> 31) | ((pp >= 2u && pp + 1u + SEED_LEN <= U.Qv.len) ? 0u : 2u));
                 }
             }
@@ -607,14 +612,14 @@ __global__ __launch_bounds__(1024) void k34_plan(const FusedUnit *__restrict__ u
     __syncthreads();
     for (uint32_t u = 0; u < nunits; u++) {
         const uint32_t nlist = (uint32_t)min((unsigned long long)NTILE, q.nheavy_u[u]);
-        const FusedUnit U = units[u];
+        const GFusedUnit U = units[u];
         for (uint32_t i0 = 0; i0 < nlist; i0 += 1024) {
             const uint32_t i = i0 + tid;
             uint32_t parts = 0, pt = 1, pq = 1, qlen = 0, tile = 0;
             if (i < nlist) {
                 tile = q.heavy[(size_t)u * NTILE + i];
                 const unsigned long long est = P.est[(size_t)u * NTILE + i];
-                const uint32_t *toff = U.T.off + (size_t)tile * TILE_WORDS, *qoff = U.Q.off + (size_t)tile * TILE_WORDS;
+                const gptr<uint32_t> toff = U.T.off + (size_t)tile * TILE_WORDS, qoff = U.Q.off + (size_t)tile * TILE_WORDS;
                 const uint32_t nT = toff[TILE_WORDS] - toff[0], nQ = qoff[TILE_WORDS] - qoff[0];
                 const uint32_t want = (uint32_t)min((unsigned long long)(1u << 20), (est + PART_HITS - 1) / PART_HITS);
                 const uint32_t groups = max(1u, (nT + 511u) / 512u);

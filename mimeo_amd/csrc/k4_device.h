@@ -98,7 +98,7 @@ __device__ __forceinline__ int32_t key_diag(const ExtQueues &q, uint64_t k, uint
 constexpr uint32_t RUN_END = 0xFFFFFFFFu;
 
 // is there a seed hit whose 19-window starts at target position p (query p - d)?
-__device__ __forceinline__ bool seed_hit_at(const StrandView &T, const StrandView &Q, int32_t p, int32_t d,
+__device__ __forceinline__ bool seed_hit_at(const GStrandView &T, const GStrandView &Q, int32_t p, int32_t d,
                                             int transitions) {
     int32_t pq = p - d;
     const Win32 tw = win32(T, p), qw = win32(Q, pq);
@@ -305,7 +305,7 @@ __device__ __forceinline__ void left_window(const uint32_t *__restrict__ tab, co
 
 // the neighbourhood of a hit: six interleaved target words from two words in front of the seed start, seven of
 // the query, brought into the target's bit frame
-__device__ __forceinline__ void load_frame(const StrandView &T, const StrandView &Q, const uint2 h, Frame &F) {
+__device__ __forceinline__ void load_frame(const GStrandView &T, const GStrandView &Q, const uint2 h, Frame &F) {
     const uint32_t bt = h.x & 31u, bq = h.y & 31u, sh = (bq - bt) & 31u;
     const int32_t wt = (int32_t)(h.x >> 5) - 2, wq = (int32_t)(h.y >> 5) - 2 - (bq < bt ? 1 : 0);
     uint4 tw[6], qw[7];
@@ -326,7 +326,7 @@ __device__ __forceinline__ void load_frame(const StrandView &T, const StrandView
 }
 
 // the score planes of the same neighbourhood from the two-plane copy (strands without N only): half the bytes
-__device__ __forceinline__ void load_frame_slim(const StrandView &T, const StrandView &Q, const uint2 h, Frame &F) {
+__device__ __forceinline__ void load_frame_slim(const GStrandView &T, const GStrandView &Q, const uint2 h, Frame &F) {
     const uint32_t bt = h.x & 31u, bq = h.y & 31u, sh = (bq - bt) & 31u;
     const int32_t wt = (int32_t)(h.x >> 5) - 2, wq = (int32_t)(h.y >> 5) - 2 - (bq < bt ? 1 : 0);
     uint2 tw[6], qw[7];
@@ -435,7 +435,7 @@ __device__ __forceinline__ FilterMasks filter_left(const Frame &F, uint32_t bt, 
 }
 
 template <int STEP, bool SLIM>
-__device__ __forceinline__ bool hit_needs_walk(const StrandView &T, const StrandView &Q, const uint2 h, int xdrop,
+__device__ __forceinline__ bool hit_needs_walk(const GStrandView &T, const GStrandView &Q, const uint2 h, int xdrop,
                                                int hspthresh, int transitions) {
     Frame F;
     if (SLIM) load_frame_slim(T, Q, h, F);  // neither strand holds an N (the host checked)
@@ -463,7 +463,7 @@ __device__ __forceinline__ bool hit_needs_walk(const StrandView &T, const Strand
 
 // the exact walk of one hit from its frame: classifies it (to the generic kernel / follower / candidate)
 template <int VARIANT>
-__device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const StrandView &T, const StrandView &Q,
+__device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const GStrandView &T, const GStrandView &Q,
                                          const uint2 h, int xdrop, int hspthresh, int transitions, bool &q_med,
                                          bool &q_fol, bool &q_cd, uint64_t &r_fk, uint32_t &r_fp, Cand &r_cd) {
     const int32_t et = (int32_t)h.x + SEED_LEN, eq = (int32_t)h.y + SEED_LEN;
@@ -473,7 +473,7 @@ __device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const
     if (VARIANT == 8) {  // loads only, with the address pattern of a two-plane (8 bytes per 32 bases) copy: timing experiment
         const uint32_t bq = h.y & 31u;
         const int32_t wt = (int32_t)(h.x >> 5) - 2, wq = (int32_t)(h.y >> 5) - 2 - (bq < bt ? 1 : 0);
-        const uint2 *t2 = reinterpret_cast<const uint2 *>(T.pw), *q2 = reinterpret_cast<const uint2 *>(Q.pw);
+        const gptr<uint2> t2 = T.pw.as<uint2>(), q2 = Q.pw.as<uint2>();
         uint32_t acc = 0;
 #pragma unroll
         for (int k = 0; k < 6; k++) { const uint2 v = t2[wt + k]; acc ^= v.x ^ v.y; }
@@ -664,7 +664,7 @@ __device__ __forceinline__ int64_t wave_max(int64_t v) {
 }
 
 // dir = -1: steps visit et-1, et-2, ...;  dir = +1: et, et+1, ...   All lanes return the same value.
-__device__ WalkResult wave_walk(const StrandView &T, const StrandView &Q, int32_t et, int32_t d, int dir,
+__device__ WalkResult wave_walk(const GStrandView &T, const GStrandView &Q, int32_t et, int32_t d, int dir,
                                 uint32_t maxsteps, int xdrop, bool detect, int transitions) {
     const uint32_t lane = threadIdx.x & 63u;
     WalkResult r{0, 0, false, 0};
@@ -717,7 +717,7 @@ __device__ WalkResult wave_walk(const StrandView &T, const StrandView &Q, int32_
 // per-base loop at all.
 constexpr int WALK_WORDS = 8;
 
-__device__ WalkResult wave_walk_fast(const StrandView &T, const StrandView &Q, int32_t et, int32_t d, int dir,
+__device__ WalkResult wave_walk_fast(const GStrandView &T, const GStrandView &Q, int32_t et, int32_t d, int dir,
                                      uint32_t maxsteps, int xdrop) {
     const uint32_t lane = threadIdx.x & 63u;
     WalkResult r{0, 0, false, 0};
@@ -822,7 +822,7 @@ struct HitRecord {
     uint32_t fprev;
     Cand c;
 };
-__device__ __forceinline__ HitRecord wave_extend_record(const StrandView &T, const StrandView &Q, uint2 h, int xdrop, int hspthresh,
+__device__ __forceinline__ HitRecord wave_extend_record(const GStrandView &T, const GStrandView &Q, uint2 h, int xdrop, int hspthresh,
                                                         int transitions, bool detect, const ExtQueues &q, uint32_t unit, uint32_t *rext_out) {
     HitRecord out;
     out.kind = 0;
@@ -883,7 +883,7 @@ __device__ __forceinline__ void stage_push(WaveStage &S, uint32_t &nf, uint32_t 
 }
 
 // ... or appended at once (lane 0)
-__device__ __forceinline__ void wave_extend_emit(const StrandView &T, const StrandView &Q, uint2 h, int xdrop, int hspthresh,
+__device__ __forceinline__ void wave_extend_emit(const GStrandView &T, const GStrandView &Q, uint2 h, int xdrop, int hspthresh,
                                                  int transitions, bool detect, const ExtQueues &q, uint32_t unit, uint32_t *rext_out) {
     const HitRecord r = wave_extend_record(T, Q, h, xdrop, hspthresh, transitions, detect, q, unit, rext_out);
     if ((threadIdx.x & 63) != 0) return;
@@ -902,7 +902,7 @@ __device__ __forceinline__ void wave_extend_emit(const StrandView &T, const Stra
 
 // per-lane walk without seed detection, windows loaded on demand; false = still alive after
 // LONG_WINDOWS windows (the caller hands the work to a wavefront)
-__device__ __forceinline__ bool lane_walk(const uint32_t *__restrict__ tab, const StrandView &T, const StrandView &Q,
+__device__ __forceinline__ bool lane_walk(const uint32_t *__restrict__ tab, const GStrandView &T, const GStrandView &Q,
                                           int32_t et, int32_t d, int dir, uint32_t limit, int xdrop, WalkState &w) {
     for (int win = 0; !w.done; win++) {
         if (win == LONG_WINDOWS) return false;

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_extend_generic(const UnitDesc 
             const uint64_t at = (uint64_t)r * q.med_cap + (gid - (r ? sh_end[r - 1] : 0));
             h = q.medq[at];
             unit = q.medu[at];
-            const StrandView T = units[unit].T, Q = units[unit].Q;
+            const GStrandView T = units[unit].T, Q = units[unit].Q;
             const int32_t et = (int32_t)h.x + SEED_LEN, eq = (int32_t)h.y + SEED_LEN;
             const int32_t d = (int32_t)h.x - (int32_t)h.y;
             // ---- left walk, with detection of an earlier seed hit at every reached boundary
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_extend_generic(const UnitDesc 
 // (k34_fused.hip); this one is kept so that two independent decompositions of the stage can be compared byte for
 // byte at full size (MIMEO_HEAVY=v1, tests/test_gpu_hsp.py).
 template <int VARIANT>
-__device__ __forceinline__ void extend_hits_body(const StrandView &T, const StrandView &Q,
+__device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GStrandView &Q,
                                                  const uint2 *__restrict__ hits, uint64_t nhits,
                                                  int xdrop, int hspthresh, int transitions,
                                                  const uint32_t *__restrict__ group_tab, const ExtQueues &q, uint32_t unit,
@@ -298,7 +298,8 @@ template <int VARIANT>
 __global__ __launch_bounds__(FAST_THREADS) void k4_walk_batch(const FusedUnit *__restrict__ funits, int xdrop, int hspthresh, int transitions,
                                                              const uint32_t *__restrict__ group_tab, ExtQueues q) {
     const FusedUnit &U = funits[blockIdx.y];
-    extend_hits_body<VARIANT>(U.Tv, U.Qv, q.walkq + U.walk_base, U.walk_cap, xdrop, hspthresh, transitions, group_tab, q, U.unit, 0,
+    const GStrandView T = U.Tv, Q = U.Qv;   // out of the table: global address space from here on (device_util.h)
+    extend_hits_body<VARIANT>(T, Q, q.walkq + U.walk_base, U.walk_cap, xdrop, hspthresh, transitions, group_tab, q, U.unit, 0,
                               q.nwalk_u + (size_t)blockIdx.y * 8);
 }
 
@@ -396,7 +397,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_resolve_small(const UnitDesc *
     uint32_t nout = 0;
     const uint32_t unit = key_unit(q, key[beg]);
     if (!big) {
-        const StrandView T = units[unit].T, Q = units[unit].Q;
+        const GStrandView T = units[unit].T, Q = units[unit].Q;
         const int32_t d = key_diag(q, key[beg], Q.len);
         const int32_t het = (int32_t)prev[beg];
         WalkState H{0, 0, 0, 0, false, false, 0};
@@ -462,7 +463,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_resolve_segments(const UnitDes
     uint64_t beg = __shfl(l_beg, src), end = __shfl(l_end, src);
     uint64_t k0 = __shfl(l_k0, src);
     const uint32_t unit = key_unit(q, k0);
-    const StrandView T = units[unit].T, Q = units[unit].Q;
+    const GStrandView T = units[unit].T, Q = units[unit].Q;
     const int32_t d = key_diag(q, k0, Q.len);
     // head: seed end = prev[beg]; only its right extent matters (it was emitted by the heavy kernel or the walks)
     int32_t het = (int32_t)__shfl(l_het, src);
@@ -510,7 +511,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_resolve_segments(const UnitDes
 __global__ __launch_bounds__(64) void k4_diag0(const UnitDesc *__restrict__ units, const uint32_t *__restrict__ selfs, ExtQueues q,
                                                int xdrop, int hspthresh, int transitions) {
     const uint32_t unit = selfs[blockIdx.x];
-    const StrandView T = units[unit].T, Q = units[unit].Q;
+    const GStrandView T = units[unit].T, Q = units[unit].Q;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nwords = (T.len + 31u) >> 5;
     uint32_t p = 0;  // first seed start still to be considered
@@ -587,7 +588,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_entropy(const UnitDesc *__rest
         }
     }
     const bool deferred = live && c.len == 0;
-    const StrandView T = units[c.unit].T, Q = units[c.unit].Q;
+    const GStrandView T = units[c.unit].T, Q = units[c.unit].Q;
     int64_t raw = c.raw;
     const int32_t d = (int32_t)c.tstart - (int32_t)c.qstart;
     // the longest candidate of the wavefront sets the number of steps (wave-uniform loops: shuffles inside)
@@ -668,7 +669,7 @@ __global__ __launch_bounds__(256) void k4_entropy_big(const UnitDesc *__restrict
     __shared__ unsigned long long red[5];
     for (uint64_t bi = blockIdx.y; bi < nbig; bi += gridDim.y) {
         const Cand c = q.cand[q.bigcand[bi]];
-        const StrandView T = units[c.unit].T, Q = units[c.unit].Q;
+        const GStrandView T = units[c.unit].T, Q = units[c.unit].Q;
         const int32_t d = (int32_t)c.tstart - (int32_t)c.qstart;
         unsigned long long cnt[4] = {0, 0, 0, 0};
         long long sum = 0;

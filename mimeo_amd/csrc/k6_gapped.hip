@@ -113,7 +113,7 @@ __device__ __forceinline__ Best4 wave_best(Best4 v) {
 // WSTRIP query bits for columns jb .. jb+WSTRIP-1 (bit s <-> column jb+s); column j consumes query base
 // aq + j - 1 (dir > 0) or aq - j (dir < 0).  Out-of-range columns read padding and are never used.
 template <int WSTRIP>
-__device__ __forceinline__ void load_qbits(const StrandView &Q, uint32_t aq, int dir, uint32_t jb, uint32_t lenB,
+__device__ __forceinline__ void load_qbits(const GStrandView &Q, uint32_t aq, int dir, uint32_t jb, uint32_t lenB,
                                            uint32_t &qlo, uint32_t &qhi, uint32_t &qn) {
     constexpr uint32_t SMASK = WSTRIP == 32 ? 0xFFFFFFFFu : ((1u << (WSTRIP & 31)) - 1u);  // WSTRIP in {4, 16, 32}
     if (jb > lenB) { qlo = qhi = qn = 0; return; }
@@ -134,7 +134,7 @@ __device__ __forceinline__ void load_qbits(const StrandView &Q, uint32_t aq, int
 // Target bases of 32 consecutive DP rows i0 .. i0+31 (bit b <-> row i0 + b): one window load per 32 rows
 // instead of a dependent global load in every row; the caller fetches one block ahead.
 struct RowBases { uint32_t lo, hi, nm; };
-__device__ __forceinline__ RowBases load_row_bases(const StrandView &T, uint32_t at, int dir, uint32_t i0) {
+__device__ __forceinline__ RowBases load_row_bases(const GStrandView &T, uint32_t at, int dir, uint32_t i0) {
     if (dir > 0) {
         const Win32 w = win32(T, (int32_t)(at + i0 - 1u));
         return RowBases{w.lo, w.hi, w.nm};
@@ -144,7 +144,7 @@ __device__ __forceinline__ RowBases load_row_bases(const StrandView &T, uint32_t
 }
 
 template <int WSTRIP>
-__device__ HalfResult wave_half_extend(const StrandView &T, const StrandView &Q, uint32_t at, uint32_t aq, int dir,
+__device__ HalfResult wave_half_extend(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir,
                                        int32_t O, int32_t E, int32_t Y, int32_t cap) {
     constexpr int WINDOW = 64 * WSTRIP;  // columns in the sliding window
     constexpr int WSHIFT = WSTRIP == 32 ? 5 : 4;
@@ -364,7 +364,7 @@ struct C4Shared {
     int flag;
 };
 
-__device__ HalfResult block_half_extend(C4Shared &sh, const StrandView &T, const StrandView &Q, uint32_t at, uint32_t aq,
+__device__ HalfResult block_half_extend(C4Shared &sh, const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq,
                                         int dir, int32_t O, int32_t E, int32_t Y) {
     constexpr int WS = C4_WS;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -658,7 +658,7 @@ __device__ __forceinline__ int32_t lean_row(LeanState &S, uint32_t srow, int32_t
     return rowmax;
 }
 
-__device__ HalfResult wave_half_extend_lean(const StrandView &T, const StrandView &Q, uint32_t at, uint32_t aq, int dir,
+__device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir,
                                             int32_t O, int32_t E, int32_t Y) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t lenA = dir > 0 ? T.len - at : at, lenB = dir > 0 ? Q.len - aq : aq;
@@ -812,7 +812,7 @@ __global__ __launch_bounds__(C4_THREADS) void k6_dp4(const Group *__restrict__ g
 constexpr uint32_t ANCHOR_W = 31, ANCHOR_CHUNK = 4096;
 constexpr int ANCHOR_THREADS = 1024;
 
-__device__ void wave_anchor_chunk(const StrandView &T, const StrandView &Q, const mimeo_hsp &h, uint32_t chunk,
+__device__ void wave_anchor_chunk(const GStrandView &T, const GStrandView &Q, const mimeo_hsp &h, uint32_t chunk,
                                   unsigned long long *packed) {
     const uint32_t lane = threadIdx.x & 63u, nw = h.length - ANCHOR_W + 1;
     const int32_t d = (int32_t)h.tstart - (int32_t)h.qstart;
@@ -1044,7 +1044,7 @@ __global__ __launch_bounds__(ANY_THREADS) void k6_dp_any(const Group *__restrict
     __shared__ uint32_t s_first[ANY_THREADS / 64], s_last[ANY_THREADS / 64];
     const DpJob job = jobs[list[first + blockIdx.x]];
     const Group &G = groups[job.group];
-    const StrandView &T = G.T, &Q = G.Q;
+    const GStrandView T = G.T, Q = G.Q;
     const uint32_t at = job.at, aq = job.aq;
     const int dir = job.dir;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -1222,7 +1222,7 @@ __global__ __launch_bounds__(TR_THREADS) void k6_trace(const Group *__restrict__
     const TraceJob J = tjobs[k];
     const HalfResult hr = res[job.slot];
     const Group &G = groups[job.group];
-    const StrandView &T = G.T, &Q = G.Q;
+    const GStrandView T = G.T, Q = G.Q;
     const uint32_t at = job.at, aq = job.aq;
     const int dir = job.dir;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
