@@ -53,14 +53,19 @@ enum { MIMEO_STRAND_PLUS = 1, MIMEO_STRAND_MINUS = 2, MIMEO_STRAND_BOTH = 3 };
  *                     (alignment specification v1, rule 6; the default)
  *   MIMEO_ANCHOR_PATH an anchor on a match/mismatch column of the path of an earlier alignment of its
  *                     (pair, strand): lastz's documented --gapped rule.  lastz also bounds a new extension
- *                     by earlier alignments; that part is not implemented. */
+ *                     by earlier alignments: mimeo_params.bound_extensions adds that (opt-in, path rule only;
+ *                     the project's own statement of it, parity unpinned; DESIGN.md §2 rule 7). */
 enum { MIMEO_ANCHOR_BOX = 0, MIMEO_ANCHOR_PATH = 1 };
 
 /*
  * Alignment parameters == the lastz flags the reference passes
  * (wrappers.py:1025-1037 / 786-798 / 607-653) plus the LASTZ defaults they imply.
  * mimeo_params_default() fills the values in brackets.  anchor_rule selects the skip rule of
- * the gapped stage (MIMEO_ANCHOR_*); any other value is MIMEO_ERR_ARG.
+ * the gapped stage (MIMEO_ANCHOR_*); any other value is MIMEO_ERR_ARG.  bound_extensions = 1 (only with
+ * MIMEO_ANCHOR_PATH; anything else is MIMEO_ERR_ARG) bounds every gapped extension by the earlier alignments of its
+ * (pair, strand): a DP cell on or beyond the nearest earlier path on either side of the anchor's diagonal is dead, so
+ * the alignments of a (pair, strand) neither cross nor run onto each other.  It took the first reserved slot: size and
+ * the other offsets are unchanged.
  */
 typedef struct mimeo_params {
     int32_t hspthresh;    /* --hspthresh [3000]; also the gapped threshold (lastz default)  */
@@ -74,7 +79,8 @@ typedef struct mimeo_params {
     int32_t gapped;       /* --gapped [1]                                                 */
     int32_t strand;       /* --strand [MIMEO_STRAND_BOTH]                                 */
     int32_t anchor_rule;  /* gapped-stage skip rule [MIMEO_ANCHOR_BOX]                    */
-    int32_t reserved[5];
+    int32_t bound_extensions; /* bound extensions by earlier alignments [0]; 1 needs MIMEO_ANCHOR_PATH */
+    int32_t reserved[4];
 } mimeo_params;
 
 /* One raw seed hit: 0-based starts of the 19-base seed window (12of19, lastz default seed). */

@@ -37,8 +37,19 @@ def add_common(parser, prog, gff_default, label, prefix, with_b):
     parser.add_argument('--anchorRule', type=str, default='box', choices=['box', 'path'],
                         help='Which anchors the gapped stage skips. box (default): an anchor inside the box of an earlier '
                              'alignment of its pair and strand. path: an anchor on a match/mismatch column of the path of an '
-                             'earlier alignment (lastz\'s --gapped rule); unlike lastz, a new extension is not bounded by '
+                             'earlier alignment (lastz\'s --gapped rule); --boundExtensions adds lastz\'s bounding of a new extension by '
                              'earlier alignments. Ignored with --recycle when the alignment file exists.')
+    parser.add_argument('--boundExtensions', action='store_true', default=False,
+                        help='With --anchorRule path: bound every gapped extension by the earlier alignments of its pair and '
+                             'strand, so that they neither cross nor run onto each other (the project\'s own statement of '
+                             'lastz\'s behaviour; parity unpinned). An error without --anchorRule path.')
+
+
+def check_common(parser, args):
+    """cross-flag rules of add_common (parser.error exits with status 2)"""
+    if args.boundExtensions and args.anchorRule != 'path':
+        parser.error('--boundExtensions needs --anchorRule path')
+    return args
 
 
 def init_logging(level):

@@ -27,6 +27,21 @@ class Params(C.Structure):
                                          'entropy', 'chain', 'gapped', 'strand', 'anchor_rule')] + \
                [('reserved', C.c_int32 * 5)]
 
+    # mimeo_params.bound_extensions took the first reserved slot of the C struct (include/mimeo_hip.h); the ctypes layout
+    # keeps the five-slot array
+    @property
+    def bound_extensions(self):
+        return int(self.reserved[0])
+
+    @bound_extensions.setter
+    def bound_extensions(self, v):
+        self.reserved[0] = int(v)
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n != 'reserved'}
+        d['bound_extensions'] = self.bound_extensions
+        return d
+
 
 ANCHOR_BOX, ANCHOR_PATH = 0, 1   # Params.anchor_rule (MIMEO_ANCHOR_*)
 ANCHOR_RULES = {'box': ANCHOR_BOX, 'path': ANCHOR_PATH}

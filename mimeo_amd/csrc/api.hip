@@ -84,6 +84,7 @@ int mimeo_params_default(mimeo_params *p) {
     p->hspthresh = 3000; p->xdrop = 910; p->ydrop = 9400; p->gap_open = 400; p->gap_extend = 30;
     p->transitions = 1; p->entropy = 1; p->chain = 1; p->gapped = 1; p->strand = MIMEO_STRAND_BOTH;
     p->anchor_rule = MIMEO_ANCHOR_BOX;
+    p->bound_extensions = 0;
     return MIMEO_OK;
 }
 
@@ -198,6 +199,15 @@ static int check_params(const mimeo_params *p) {
     if (!(p->strand & MIMEO_STRAND_BOTH)) { set_error("strand selects nothing"); return MIMEO_ERR_ARG; }
     if (p->anchor_rule != MIMEO_ANCHOR_BOX && p->anchor_rule != MIMEO_ANCHOR_PATH) {
         set_error("anchor_rule must be MIMEO_ANCHOR_BOX (0) or MIMEO_ANCHOR_PATH (1)");
+        return MIMEO_ERR_ARG;
+    }
+    if (p->bound_extensions != 0 && p->bound_extensions != 1) { set_error("bound_extensions must be 0 or 1"); return MIMEO_ERR_ARG; }
+    if (p->bound_extensions && p->anchor_rule != MIMEO_ANCHOR_PATH) {
+        set_error("bound_extensions needs anchor_rule = MIMEO_ANCHOR_PATH (1)");
+        return MIMEO_ERR_ARG;
+    }
+    if (p->bound_extensions && getenv("MIMEO_K6_KERNEL")) {
+        set_error("bound_extensions: the development kernels of MIMEO_K6_KERNEL have no bounded form");
         return MIMEO_ERR_ARG;
     }
     return 0;

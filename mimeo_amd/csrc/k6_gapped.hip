@@ -22,6 +22,10 @@
 //     the path of an earlier alignment.  After a round's DP kernels k6_trace re-runs the round's halves with a traceback,
 //     checks them against the first run and leaves each path as gap-free blocks; k6_pick / k6_resolve<true> test the
 //     blocks of the alignments whose box holds the anchor.  The box-rule kernels are unchanged.
+//   * bounded extensions (mimeo_params.bound_extensions = 1, opt-in, path rule only; parity unpinned): a DP cell on or beyond the
+//     nearest earlier path on either side of the anchor's diagonal is dead (alignment specification v1, rule 7; the specification is
+//     tests/bounded_oracle.c).  k6_dp1_bounded / k6_dp_any<true> / k6_trace<true> look the bounds up row range by row range
+//     (bounds_at); k6_resolve<true, true> sends an anchor back when an alignment accepted after its DP ran reaches into what it swept.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -539,6 +543,110 @@ __device__ HalfResult block_half_extend(C4Shared &sh, const GStrandView &T, cons
     return best;
 }
 
+struct PathBlock {
+    uint32_t t, q, len;
+};
+constexpr uint32_t PATH_UNTRACED = 0xFFFFFFFFu;  // pidx[slot].x of a half whose traceback did not fit the trace pool
+struct PathView {
+    const uint2 *pidx;       // per half slot (as HalfResult): first block in blk, block count
+    const PathBlock *blk;    // block arena of the call
+    uint32_t *accrank;       // per alignment slot hsp_begin + e: rank of its anchor (written by k6_resolve)
+};
+
+// ---- bounds (mimeo_params.bound_extensions; path rule only) -------------------------------------------------------------
+// A half extension of an anchor (at, aq) is bounded by the diagonal steps of the alignments accepted so far in its group
+// (alignment specification v1, rule 7): with d0 = aq - at and, for the target base t of DP row i, dL / dR the nearest
+// earlier diagonals q - t at or below / at or above d0, cell (i, j) lives only if dL < q_j - t < dR.  In the DP's own
+// diagonal index k = j - i that is an open interval (kmin, kmax), piecewise constant in i: it changes only where a block
+// of an earlier path starts or ends.  The DP kernels carry the interval and the next row where it may change as
+// wave-uniform scalars and ask bounds_at() again when they get there: one lane per accepted alignment whose box holds
+// the row, one binary search in that alignment's blocks.  Nothing is precomputed, so rows a half never reaches cost nothing.
+struct BoundCtx {
+    const mimeo_alignment *aln;   // the alignments of group g at aln[hsp_begin .. + nacc), strand coordinates
+    const uint2 *anchors;
+    PathView P;
+};
+constexpr long long K_INF = 1ll << 40;   // beyond every diagonal difference
+struct RowBound {
+    long long kmin, kmax;   // cell (i, j) is allowed iff kmin < j - i < kmax
+    uint32_t next;          // first row above i where the interval may differ
+    uint32_t any;           // some earlier path has a diagonal step in row i
+};
+struct HalfSweep {   // what a bounded half extension looked at (k6_resolve: is the result still valid?)
+    int32_t klo, khi;    // smallest / largest k = j - i of a live cell in rows >= 1 (strip granularity in k6_dp1: a superset)
+    uint32_t nacc;       // alignments of the group it was bounded by (the group's nacc when its DP ran)
+    uint32_t nbound;     // rows in which an earlier path set a bound
+};
+__device__ __forceinline__ long long wave_uniform_ll(long long v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(unsigned long long)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+// wave-cooperative; every lane returns the same.  Row i >= 1 of the half (at, aq, dir); i is at most the half's target length.
+__device__ __forceinline__ RowBound bounds_at(const BoundCtx &B, uint64_t b0, uint32_t nacc, uint32_t at, uint32_t aq, int dir, uint32_t i) {
+    const long long t = dir > 0 ? (long long)at + i - 1 : (long long)at - i;
+    const long long d0 = (long long)aq - (long long)at;
+    long long kmin = -K_INF, kmax = K_INF;
+    long long nt = dir > 0 ? K_INF : -1;   // next target base, in the direction of travel, where a block starts or ends
+    for (uint32_t e = threadIdx.x & 63u; e < nacc; e += 64u) {
+        const mimeo_alignment o = B.aln[b0 + e];
+        long long c;
+        if (t >= (long long)o.tstart && t < (long long)o.tend) {
+            const uint32_t rank = B.P.accrank[b0 + e];
+            const uint2 an = B.anchors[b0 + rank];
+            const uint32_t side = t >= (long long)an.x ? 1u : 0u;
+            const uint2 ix = B.P.pidx[2u * (b0 + rank) + side];
+            const bool traced = ix.x != PATH_UNTRACED;
+            const uint32_t n = traced ? ix.y : 0u;
+            const PathBlock *blk = B.P.blk + (traced ? ix.x : 0u);
+            uint32_t lo = 0, hi = n;   // first block that starts above t
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if ((long long)blk[mid].t <= t) lo = mid + 1; else hi = mid;
+            }
+            PathBlock b{0, 0, 0};
+            if (lo) b = blk[lo - 1];
+            if (lo && t - (long long)b.t < (long long)b.len) {   // the row holds a diagonal step of this alignment
+                const long long d = (long long)b.q - (long long)b.t, k = dir > 0 ? d - d0 : d0 - d;
+                if (k <= 0) kmin = max(kmin, k);
+                if (k >= 0) kmax = min(kmax, k);
+                c = dir > 0 ? (long long)b.t + b.len : (long long)b.t - 1;
+            } else if (dir > 0) {
+                c = lo < n ? (long long)blk[lo].t : (side == 0 ? (long long)an.x : (long long)o.tend);
+            } else {
+                c = lo ? (long long)b.t + b.len - 1 : (side == 1 ? (long long)an.x - 1 : (long long)o.tstart - 1);
+            }
+        } else if (dir > 0) {
+            c = (long long)o.tstart > t ? (long long)o.tstart : K_INF;
+        } else {
+            c = (long long)o.tend <= t ? (long long)o.tend - 1 : -1;
+        }
+        nt = dir > 0 ? min(nt, c) : max(nt, c);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        kmin = max(kmin, __shfl_xor(kmin, o));
+        kmax = min(kmax, __shfl_xor(kmax, o));
+        const long long on = __shfl_xor(nt, o);
+        nt = dir > 0 ? min(nt, on) : max(nt, on);
+    }
+    RowBound r;
+    r.kmin = wave_uniform_ll(kmin); r.kmax = wave_uniform_ll(kmax);
+    nt = wave_uniform_ll(nt);
+    const long long nrow = dir > 0 ? nt - (long long)at + 1 : (long long)at - nt;   // the row that consumes target base nt
+    r.next = nrow > 0xFFFFFFFEll ? 0xFFFFFFFFu : (uint32_t)nrow;
+    r.any = (r.kmin > -K_INF || r.kmax < K_INF) ? 1u : 0u;
+    return r;
+}
+// may a bounded half take the identical-suffix shortcut?  Only when no accepted alignment reaches into its rows
+__device__ __forceinline__ bool bounds_none(const BoundCtx &B, uint64_t b0, uint32_t nacc, uint32_t at, int dir) {
+    bool hit = false;
+    for (uint32_t e = threadIdx.x & 63u; e < nacc; e += 64u) {
+        const mimeo_alignment o = B.aln[b0 + e];
+        if (o.tend > o.tstart && (dir > 0 ? o.tend > at : o.tstart < at)) hit = true;
+    }
+    return __ballot(hit) == 0;
+}
+
 // ---- lean single-wavefront DP (k6_dp1): the production kernel -----------------------------------------------
 // Same recurrences, pruning and tie-breaks as wave_half_extend<16> (one wavefront, 16 columns per lane, 1024-column
 // window that slides by whole strips), written for VALU issue, which is what bounds K6 (profiles/r02_*: both
@@ -602,8 +710,10 @@ __device__ __forceinline__ void lean_selectors(LeanState &S, uint32_t qlo, uint3
     }
 }
 
-// one DP row; returns the lane's row maximum (NEG when none of its cells is live)
-template <bool EDGE>
+// one DP row; returns the lane's row maximum (NEG when none of its cells is live).  BND (bounded extension, with EDGE):
+// exmask also clears the slots outside the row's allowed interval, and their H is dead before the insertion pass: the
+// forbidden cells are a prefix and a suffix of the row, so H masked after pass 1 and C / D after pass 3 is the rule
+template <bool EDGE, bool BND = false>
 __device__ __forceinline__ int32_t lean_row(LeanState &S, uint32_t srow, int32_t O, int32_t E, int32_t thr, uint32_t exmask,
                                             int32_t lane_base, int32_t kneg128) {
     const int32_t OE = O + E;
@@ -623,6 +733,7 @@ __device__ __forceinline__ int32_t lean_row(LeanState &S, uint32_t srow, int32_t
         const bool vert = ds > gs;  // diagonal preferred on ties
         S.D[s] = ds; S.Dc[s] = dc;
         S.C[s] = max(gs, ds);
+        if (BND) S.C[s] = ((exmask >> s) & 1u) ? S.C[s] : NEG;
         S.Cc[s] = vert ? dc : gc;
     }
     // pass 2: the strip's aggregate of the insertion state as it arrives at the first column of the next strip
@@ -658,13 +769,18 @@ __device__ __forceinline__ int32_t lean_row(LeanState &S, uint32_t srow, int32_t
     return rowmax;
 }
 
+// BOUND: the extension is bounded by the group's nacc accepted alignments (bounds_at); *sw receives what it swept
+template <bool BOUND>
 __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir,
-                                            int32_t O, int32_t E, int32_t Y) {
+                                            int32_t O, int32_t E, int32_t Y, const BoundCtx &B, uint64_t b0, uint32_t nacc,
+                                            HalfSweep *sw) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t lenA = dir > 0 ? T.len - at : at, lenB = dir > 0 ? Q.len - aq : aq;
     HalfResult best{0, 0, 0, 0, 0, 0, 0, 0};
-    // ---- exact shortcut: identical, N-free to the end of the shorter sequence (as wave_half_extend)
-    {
+    if (BOUND) *sw = HalfSweep{0, 0, nacc, 0};
+    // ---- exact shortcut: identical, N-free to the end of the shorter sequence (as wave_half_extend); a bounded half
+    // may take it only when no earlier alignment reaches into its rows
+    if (!BOUND || bounds_none(B, b0, nacc, at, dir)) {
         const uint32_t n = min(lenA, lenB);
         const int32_t st = dir > 0 ? (int32_t)at : (int32_t)(at - n), sq = dir > 0 ? (int32_t)aq : (int32_t)(aq - n);
         bool ok = true;
@@ -726,10 +842,17 @@ __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandV
 #pragma unroll
         for (int s = 0; s < L_WS; s++) exmask |= (jb + s <= lenB ? 1u : 0u) << s;
     }
+    long long bkmin = -K_INF, bkmax = K_INF;   // BOUND: the allowed interval of k = j - i, and the row where it is looked up again
+    uint32_t bnext = 1u;
+    int32_t klo = INT32_MAX, khi = INT32_MIN;
     RowBases rbase{0, 0, 0}, rnext = load_row_bases(T, at, dir, 1u);
     for (uint32_t i = 1; i <= lenA; i++) {
         // the packed counts hold 16 bits each: a longer extension is redone by the wide kernel (unpacked counts)
         if (i >= 0xFFFFu) { best.overflow = 1; break; }
+        if (BOUND && i == bnext) {
+            const RowBound rb = bounds_at(B, b0, nacc, at, aq, dir, i);
+            bkmin = rb.kmin; bkmax = rb.kmax; bnext = rb.next;
+        }
         const int32_t thr = best.score - Y;
         const uint32_t rbit = (i - 1u) & 31u;
         if (rbit == 0) { rbase = rnext; rnext = load_row_bases(T, at, dir, i + 32u); }
@@ -738,14 +861,30 @@ __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandV
         const uint32_t a = ((rlo >> rbit) & 1u) | (((rhi >> rbit) & 1u) << 1);
         uint32_t srow = a & 2u ? (a & 1u ? tab[3] : tab[2]) : (a & 1u ? tab[1] : tab[0]);
         if ((rnm >> rbit) & 1u) srow = 0x1C1C1C1Cu;
-        const int32_t rowmax = edge ? lean_row<true>(S, srow, O, E, thr, exmask, lane_base, kneg128)
-                                    : lean_row<false>(S, srow, O, E, thr, exmask, lane_base, kneg128);
+        // BOUND: the allowed columns of this row are jlo .. jhi; only rows in which they cut the window run the masked variant
+        uint32_t bm = 0;
+        bool cut = false;
+        if (BOUND) {
+            const long long jlo = bkmin + (long long)i + 1, jhi = bkmax + (long long)i - 1;
+            if (bkmin > -K_INF || bkmax < K_INF) sw->nbound++;
+            cut = jlo > (long long)wb || jhi < (long long)wb + (L_WINDOW - 1);
+            const long long r0 = jlo - (long long)jb, r1 = jhi - (long long)jb + 1;
+            const uint32_t s0 = (uint32_t)min(max(r0, 0ll), (long long)L_WS), s1 = (uint32_t)min(max(r1, 0ll), (long long)L_WS);
+            bm = ((1u << s1) - 1u) & ~((1u << s0) - 1u) & exmask;   // exmask: all slots, or those within the query
+        }
+        const int32_t rowmax = BOUND && cut ? lean_row<true, true>(S, srow, O, E, thr, bm, lane_base, kneg128)
+                               : edge ? lean_row<true>(S, srow, O, E, thr, exmask, lane_base, kneg128)
+                                      : lean_row<false>(S, srow, O, E, thr, exmask, lane_base, kneg128);
         const uint64_t ball = __ballot(rowmax > NEGH);
         if (!ball) break;
         const uint32_t rf = (uint32_t)__builtin_ctzll(ball), rl = 63u - (uint32_t)__builtin_clzll(ball);
         if (rl == 63u) { best.overflow = 1; break; }
         best.maxcols = max(best.maxcols, (rl + 1u) * L_WS);
         best.rows = i;
+        if (BOUND) {   // the strips with a live cell, as diagonals of this row
+            klo = min(klo, (int32_t)((long long)wb + rf * L_WS - (long long)i));
+            khi = max(khi, (int32_t)((long long)wb + (rl + 1u) * L_WS - 1 - (long long)i));
+        }
         const int32_t wmax = wave_max_i32(rowmax);
         if (wmax > best.score) {
             // the cell: lowest lane holding the maximum, smallest slot in it (smallest column on ties)
@@ -782,9 +921,10 @@ __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandV
                 exmask = 0;
 #pragma unroll
                 for (int s = 0; s < L_WS; s++) exmask |= (jb + s <= lenB ? 1u : 0u) << s;
-            }
+            } else if (BOUND) exmask = (1u << L_WS) - 1u;
         }
     }
+    if (BOUND) { sw->klo = klo; sw->khi = khi; }
     return best;
 }
 
@@ -792,8 +932,24 @@ __global__ __launch_bounds__(64) void k6_dp1(const Group *__restrict__ groups, c
                                              HalfResult *__restrict__ res, int32_t O, int32_t E, int32_t Y) {
     const DpJob job = jobs[blockIdx.x];
     const Group &G = groups[job.group];
-    HalfResult r = wave_half_extend_lean(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y);
+    HalfResult r = wave_half_extend_lean<false>(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, BoundCtx{}, 0, 0, nullptr);
     if (threadIdx.x == 0) res[job.slot] = r;
+}
+
+// k6_dp1 under mimeo_params.bound_extensions.  A half that does not fit (band, rows) goes on to k6_dp_any<true>
+__global__ __launch_bounds__(64) void k6_dp1_bounded(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
+                                                     HalfResult *__restrict__ res, HalfSweep *__restrict__ sweep, int32_t O, int32_t E,
+                                                     int32_t Y, BoundCtx B, unsigned int *__restrict__ novf,
+                                                     unsigned int *__restrict__ ovf_list) {
+    const DpJob job = jobs[blockIdx.x];
+    const Group &G = groups[job.group];
+    HalfSweep sw;
+    HalfResult r = wave_half_extend_lean<true>(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, B, G.hsp_begin, G.nacc, &sw);
+    if (threadIdx.x == 0) {
+        res[job.slot] = r;
+        sweep[job.slot] = sw;
+        if (r.overflow) ovf_list[atomicAdd(novf, 1u)] = blockIdx.x;
+    }
 }
 
 __global__ __launch_bounds__(C4_THREADS) void k6_dp4(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
@@ -892,15 +1048,7 @@ __device__ __forceinline__ bool in_boxes(const mimeo_alignment *aln, uint32_t n,
 // The path of an alignment = its diagonal (match / mismatch) steps from both halves, kept as gap-free blocks (t, q, len)
 // sorted by t.  A half's diagonal steps have distinct t (each consumes one target base) and the left half lies below the
 // anchor's t, the right half at or above it, so one binary search per half decides whether (t, q) is on the path.
-struct PathBlock {
-    uint32_t t, q, len;
-};
-constexpr uint32_t PATH_UNTRACED = 0xFFFFFFFFu;  // pidx[slot].x of a half whose traceback did not fit the trace pool
-struct PathView {
-    const uint2 *pidx;       // per half slot (as HalfResult): first block in blk, block count
-    const PathBlock *blk;    // block arena of the call
-    uint32_t *accrank;       // per alignment slot hsp_begin + e: rank of its anchor (written by k6_resolve)
-};
+// (PathBlock / PathView are defined further up, ahead of the bounded DP that reads them.)
 __device__ __forceinline__ bool on_half_path(const PathBlock *blk, uint32_t n, uint2 a) {
     uint32_t lo = 0, hi = n;  // first block with t > a.x
     while (lo < hi) {
@@ -1035,10 +1183,13 @@ __device__ __forceinline__ AnyRow any_row(uint32_t *base, uint32_t parity) {
 }
 constexpr size_t ANY_SLOT_WORDS = 2u * 6u * (size_t)ANY_COLS;  // per job
 
+// BOUND (mimeo_params.bound_extensions): cells outside the row's allowed interval (bounds_at) are dead in all three states
+template <bool BOUND>
 __global__ __launch_bounds__(ANY_THREADS) void k6_dp_any(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
                                                          const unsigned int *__restrict__ list, uint32_t first,
                                                          HalfResult *__restrict__ res, uint32_t *__restrict__ scratch,
-                                                         int32_t O, int32_t E, int32_t Y, int32_t cap) {
+                                                         int32_t O, int32_t E, int32_t Y, int32_t cap, BoundCtx B,
+                                                         HalfSweep *__restrict__ sweep) {
     __shared__ Cell s_scan[ANY_THREADS / 64];
     __shared__ Best4 s_best[ANY_THREADS / 64];
     __shared__ uint32_t s_first[ANY_THREADS / 64], s_last[ANY_THREADS / 64];
@@ -1067,8 +1218,19 @@ __global__ __launch_bounds__(ANY_THREADS) void k6_dp_any(const Group *__restrict
     }
     __syncthreads();
     uint32_t par = 0;
+    const uint64_t b0 = G.hsp_begin;
+    const uint32_t nacc = BOUND ? G.nacc : 0u;
+    long long bkmin = -K_INF, bkmax = K_INF;
+    uint32_t bnext = 1u, nbound = 0;
+    int32_t klo = INT32_MAX, khi = INT32_MIN;
     for (uint32_t i = 1; i <= lenA && !overflow; i++, par ^= 1u) {
         const AnyRow P = any_row(base, par), N = any_row(base, par ^ 1u);
+        if (BOUND && i == bnext) {
+            const RowBound rb = bounds_at(B, b0, nacc, at, aq, dir, i);
+            bkmin = rb.kmin; bkmax = rb.kmax; bnext = rb.next;
+        }
+        if (BOUND && (bkmin > -K_INF || bkmax < K_INF)) nbound++;
+        const long long jlo = bkmin + (long long)i + 1, jhi = bkmax + (long long)i - 1;   // the allowed columns
         const int32_t thr = best.score - Y;
         const int32_t pa = dir > 0 ? (int32_t)(at + i - 1) : (int32_t)(at - i);
         const Base1 ab = base_at(T, pa);
@@ -1098,6 +1260,7 @@ __global__ __launch_bounds__(ANY_THREADS) void k6_dp_any(const Group *__restrict
                     g.nx = P.cx[(j - 1) & M] + (m ? 0u : 1u);
                 }
             }
+            if (BOUND && ((long long)j < jlo || (long long)j > jhi)) { dd.s = NEG; g.s = NEG; }
             N.ds[j & M] = dd.s; N.dm[j & M] = dd.nm; N.dx[j & M] = dd.nx;
             Cell hh = g;  // diagonal preferred on ties
             if (dd.s > g.s) hh = dd;
@@ -1123,7 +1286,7 @@ __global__ __launch_bounds__(ANY_THREADS) void k6_dp_any(const Group *__restrict
             acc = cmax_left(acc, u);
             Cell c = hh;  // H preferred over I on ties
             if (I.s > c.s) c = I;
-            const bool alive = c.s >= thr && c.s > NEGH;
+            const bool alive = c.s >= thr && c.s > NEGH && (!BOUND || ((long long)j >= jlo && (long long)j <= jhi));
             N.cs[j & M] = alive ? c.s : NEG; N.cm[j & M] = c.nm; N.cx[j & M] = c.nx;
             if (!alive) N.ds[j & M] = NEG;
             if (alive) {
@@ -1152,6 +1315,10 @@ __global__ __launch_bounds__(ANY_THREADS) void k6_dp_any(const Group *__restrict
         hi = last1 - 1u;
         best.maxcols = max(best.maxcols, hi - lo + 1u);
         best.rows = i;
+        if (BOUND) {
+            klo = min(klo, (int32_t)((long long)lo - (long long)i));
+            khi = max(khi, (int32_t)((long long)hi - (long long)i));
+        }
         if (tb.s > best.score) { best.score = tb.s; best.i = i; best.j = tb.j; best.nm = tb.nm; best.nx = tb.nx; }
         // The cells are 32 bits wide (as lastz's own score_t, which wraps there).  Every live cell of a row lies within the
         // y-drop of the best score so far, so when that nears the cap the whole row — and the best score — is moved down by
@@ -1172,6 +1339,7 @@ __global__ __launch_bounds__(ANY_THREADS) void k6_dp_any(const Group *__restrict
     best.base_hi = (uint32_t)((unsigned long long)sbase >> 32);
     best.overflow = overflow ? 1u : 0u;
     if (tid == 0) res[job.slot] = best;
+    if (BOUND && tid == 0) sweep[job.slot] = HalfSweep{klo, khi, nacc, nbound};
 }
 
 // ---- traceback of a half extension (path rule) -------------------------------------------------------------------------
@@ -1206,12 +1374,14 @@ __host__ __device__ inline TraceLayout trace_layout(uint32_t rows, uint32_t W, u
 // errors of the trace (ctr[1]): the re-run or the walk disagrees with the first run; ctr[2] = the half's slot
 enum : uint32_t { TRERR_DP = 1, TRERR_WALK = 2, TRERR_ROOM = 3 };
 
+// BOUND: the re-run is bounded as the first run was (the group's nacc has not moved since: same round, before k6_resolve)
+template <bool BOUND>
 __global__ __launch_bounds__(TR_THREADS) void k6_trace(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
                                                        const TraceJob *__restrict__ tjobs, uint32_t k0,
                                                        const HalfResult *__restrict__ res, uint8_t *__restrict__ pool,
                                                        PathBlock *__restrict__ arena, unsigned long long arena_cap,
                                                        uint2 *__restrict__ pidx, unsigned int *__restrict__ ctr,
-                                                       int32_t O, int32_t E, int32_t Y) {
+                                                       int32_t O, int32_t E, int32_t Y, BoundCtx B) {
     __shared__ int32_t s_ring[4 * TR_LDS_COLS];
     __shared__ Cell s_scan[TR_THREADS / 64];
     __shared__ Best4 s_best[TR_THREADS / 64];
@@ -1262,8 +1432,17 @@ __global__ __launch_bounds__(TR_THREADS) void k6_trace(const Group *__restrict__
     __syncthreads();
     bool bad = hi + 2u > M;
     uint32_t par = 0;
+    const uint64_t b0 = G.hsp_begin;
+    const uint32_t nacc = BOUND ? G.nacc : 0u;
+    long long bkmin = -K_INF, bkmax = K_INF;
+    uint32_t bnext = 1u;
     for (uint32_t i = 1; i <= rows && !bad; i++, par ^= 1u) {
         int32_t *Pc = cs[par], *Pd = ds[par], *Nc = cs[par ^ 1u], *Nd = ds[par ^ 1u];
+        if (BOUND && i == bnext) {
+            const RowBound rb = bounds_at(B, b0, nacc, at, aq, dir, i);
+            bkmin = rb.kmin; bkmax = rb.kmax; bnext = rb.next;
+        }
+        const long long jlo = bkmin + (long long)i + 1, jhi = bkmax + (long long)i - 1;   // the allowed columns
         const int32_t thr = best - Y;
         const Base1 ab = base_at(T, dir > 0 ? (int32_t)(at + i - 1) : (int32_t)(at - i));
         const uint32_t hx = min(lenB, hi + 1u + ext);
@@ -1289,6 +1468,7 @@ __global__ __launch_bounds__(TR_THREADS) void k6_trace(const Group *__restrict__
                     g = pc + sub_score(ab.lo ^ qb.lo, ab.hi ^ qb.hi, ab.lo ^ ab.hi, ab.nm | qb.nm);
                 }
             }
+            if (BOUND && ((long long)j < jlo || (long long)j > jhi)) { dd = NEG; g = NEG; }
             Nd[j & M] = dd;
             int32_t hh = g;  // diagonal preferred on ties
             if (dd > g) { hh = dd; bits |= TB_HD; }
@@ -1316,7 +1496,7 @@ __global__ __launch_bounds__(TR_THREADS) void k6_trace(const Group *__restrict__
             if (u > acc.s) { acc.s = u; acc.nm = j; }
             int32_t c = hh;  // H preferred over I on ties
             if (I > c) { c = I; bits |= TB_CI; }
-            const bool alive = c >= thr && c > NEGH;
+            const bool alive = c >= thr && c > NEGH && (!BOUND || ((long long)j >= jlo && (long long)j <= jhi));
             Nc[j & M] = alive ? c : NEG;
             if (!alive) Nd[j & M] = NEG;
             trow[j] |= bits;
@@ -1415,10 +1595,40 @@ __global__ void k6_trace_gather(const DpJob *__restrict__ jobs, uint32_t n, cons
 
 // one wave per group: finalise anchors in rank order as far as DP results exist
 constexpr uint32_t RESOLVE_NEW = 256;  // boxes accepted per invocation that fit the LDS list
-template <bool PATH>
+
+// bounded extensions: does the alignment of the anchor of rank `rank` (box o: tstart, tend, qstart, qend) put a bound
+// into the cells that the halves L / R of anchor a looked at?  Yes iff one of its blocks covers an evaluated row of a half
+// and its diagonal lies within the k that half swept.  Wave-cooperative (lanes over the blocks).
+__device__ __forceinline__ bool bounds_touch(const PathView &P, const uint2 *anchors, uint64_t b0, uint32_t rank, uint4 o, uint2 a,
+                                             const HalfResult &L, const HalfResult &R, const HalfSweep &sL, const HalfSweep &sR) {
+    const uint32_t rowsL = L.rows ? L.rows : L.i, rowsR = R.rows ? R.rows : R.i;   // rows == 0, i > 0: the shortcut's diagonal
+    const long long tlo = (long long)a.x - rowsL, thi = (long long)a.x + rowsR;    // target bases the two halves consumed
+    if ((long long)o.y <= tlo || (long long)o.x >= thi) return false;
+    const long long d0 = (long long)a.y - (long long)a.x;
+    bool hit = false;
+    for (uint32_t side = 0; side < 2; side++) {
+        const uint2 ix = P.pidx[2u * (b0 + rank) + side];
+        if (ix.x == PATH_UNTRACED) continue;
+        for (uint32_t k = threadIdx.x & 63u; k < ix.y; k += 64u) {
+            const PathBlock b = P.blk[ix.x + k];
+            const long long t0 = b.t, t1 = (long long)b.t + b.len, d = (long long)b.q - (long long)b.t;
+            if (t0 < thi && t1 > (long long)a.x && d - d0 >= sR.klo && d - d0 <= sR.khi) hit = true;
+            if (t0 < (long long)a.x && t1 > tlo && d0 - d >= sL.klo && d0 - d <= sL.khi) hit = true;
+        }
+    }
+    return __ballot(hit) != 0;
+}
+
+// BOUND (mimeo_params.bound_extensions, with PATH): the rule is sequential — rank r is bounded by everything accepted
+// below r — but a round's DPs ran against the alignments accepted when the round began (HalfSweep.nacc).  Before rank r
+// is accepted, every alignment accepted since is tested against what r's halves swept (bounds_touch); if one touches,
+// the result is stale: the anchor goes back to A_NEW and the group's resolve stops there, so the next round runs it
+// again as the group's lowest unfinalised anchor, which is always bounded by exactly the alignments below it.
+template <bool PATH, bool BOUND = false>
 __global__ __launch_bounds__(64) void k6_resolve(Group *__restrict__ groups, const uint2 *__restrict__ anchors,
                                                  const HalfResult *__restrict__ res, mimeo_alignment *__restrict__ aln,
-                                                 uint8_t *__restrict__ astate, unsigned int *__restrict__ remaining, PathView P) {
+                                                 uint8_t *__restrict__ astate, unsigned int *__restrict__ remaining, PathView P,
+                                                 const HalfSweep *__restrict__ sweep) {
     __shared__ uint4 sbox[RESOLVE_NEW];  // boxes accepted in this invocation (tstart, tend, qstart, qend)
     __shared__ uint32_t srank[PATH ? RESOLVE_NEW : 1];  // ... and the ranks of their anchors (path rule)
     Group &G = groups[blockIdx.x];
@@ -1447,6 +1657,20 @@ __global__ __launch_bounds__(64) void k6_resolve(Group *__restrict__ groups, con
         if (st == A_NEW) break;  // not swallowed and no DP result yet: it is scheduled in the next round
         const uint32_t slot = 2u * (uint32_t)(b0 + r);
         HalfResult L = res[slot], R = res[slot + 1];
+        if (BOUND && !(L.overflow | R.overflow)) {
+            const HalfSweep sL = sweep[slot], sR = sweep[slot + 1];
+            bool stale = false;
+            for (uint32_t e = sL.nacc; e < nacc0 && !stale; e++) {
+                const mimeo_alignment &o = aln[b0 + e];
+                stale = bounds_touch(P, anchors, b0, P.accrank[b0 + e], make_uint4(o.tstart, o.tend, o.qstart, o.qend), a, L, R, sL, sR);
+            }
+            for (uint32_t e = 0; e < nnew && !stale; e++)
+                stale = bounds_touch(P, anchors, b0, srank[PATH ? e : 0], sbox[e], a, L, R, sL, sR);
+            if (stale) {
+                if (threadIdx.x == 0) { astate[b0 + r] = A_NEW; atomicAdd(remaining + 2, 1u); }
+                break;
+            }
+        }
         overflow |= L.overflow | R.overflow;
         // path rule: a half without a traceback (larger than the trace pool) fails the group like a band beyond the limit
         if (PATH && (P.pidx[slot].x == PATH_UNTRACED || P.pidx[slot + 1].x == PATH_UNTRACED)) overflow = 1;
@@ -1557,6 +1781,14 @@ void dense_alignments_device(Group *d_groups, uint32_t ngroups, const mimeo_alig
 static DeviceBuf g_anchors, g_packed, g_jobs, g_res, g_cnt, g_astate, g_ovf_list, g_any;
 // path rule: per half slot (first block, count), per alignment slot the anchor's rank, the block arena, the trace pool
 static DeviceBuf g_pidx, g_accrank, g_arena, g_pool, g_tjobs, g_tres, g_tctr;
+static DeviceBuf g_sweep;   // bounded extensions: per half slot what its DP swept (HalfSweep)
+
+// bounded extensions with penalties outside the lean kernel's domain: every job of the round goes to k6_dp_any<true>
+__global__ void k6_list_all(uint32_t n, unsigned int *__restrict__ novf, unsigned int *__restrict__ ovf_list) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) ovf_list[k] = k;
+    if (k == 0) *novf = n;
+}
 
 // bytes of traceback the path rule may hold at once: a share of the free device memory (like the queue arenas of K4);
 // MIMEO_K6_TRACE_POOL_MB sets it (tests: force slices, or a pool too small for one half)
@@ -1586,7 +1818,7 @@ static int arena_reserve(uint64_t blocks, uint64_t used) {
 // tracebacks fit the pool together.  A half whose traceback alone exceeds the pool gets no path (PATH_UNTRACED): k6_resolve
 // fails its group if the anchor is accepted, as for a band beyond the DP limit.
 static int trace_round(Group *d_groups, uint32_t h0, const mimeo_params *p, uint64_t budget, uint64_t *arena_used, float *ms,
-                       uint32_t *slices, uint64_t *largest) {
+                       uint32_t *slices, uint64_t *largest, bool bounded, BoundCtx bc) {
     hipStream_t st = stream();
     int rc;
     if ((rc = g_tres.reserve((size_t)h0 * sizeof(HalfResult)))) return rc;
@@ -1633,12 +1865,20 @@ static int trace_round(Group *d_groups, uint32_t h0, const mimeo_params *p, uint
     static hipEvent_t e0 = nullptr, e1 = nullptr;
     if (!e0) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
     HIP_TRY(hipEventRecord(e0, st));
+    bc.P.blk = (const PathBlock *)g_arena.p;   // the arena may just have grown
     for (size_t c = 0; c + 1 < cut.size(); c++)
-        if (cut[c + 1] > cut[c] && ++*slices)
-            hipLaunchKernelGGL(k6_trace, dim3(cut[c + 1] - cut[c]), dim3(TR_THREADS), 0, st, (const Group *)d_groups,
-                               (const DpJob *)g_jobs.p, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
-                               (uint8_t *)g_pool.p, (PathBlock *)g_arena.p, (unsigned long long)(g_arena.cap / sizeof(PathBlock)),
-                               (uint2 *)g_pidx.p, (unsigned int *)g_tctr.p, O, E, Y);
+        if (cut[c + 1] > cut[c] && ++*slices) {
+            if (bounded)
+                hipLaunchKernelGGL(k6_trace<true>, dim3(cut[c + 1] - cut[c]), dim3(TR_THREADS), 0, st, (const Group *)d_groups,
+                                   (const DpJob *)g_jobs.p, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
+                                   (uint8_t *)g_pool.p, (PathBlock *)g_arena.p, (unsigned long long)(g_arena.cap / sizeof(PathBlock)),
+                                   (uint2 *)g_pidx.p, (unsigned int *)g_tctr.p, O, E, Y, bc);
+            else
+                hipLaunchKernelGGL(k6_trace<false>, dim3(cut[c + 1] - cut[c]), dim3(TR_THREADS), 0, st, (const Group *)d_groups,
+                                   (const DpJob *)g_jobs.p, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
+                                   (uint8_t *)g_pool.p, (PathBlock *)g_arena.p, (unsigned long long)(g_arena.cap / sizeof(PathBlock)),
+                                   (uint2 *)g_pidx.p, (unsigned int *)g_tctr.p, O, E, Y, bc);
+        }
     HIP_TRY(hipEventRecord(e1, st));
     unsigned int c3[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(c3, g_tctr.p, 12, hipMemcpyDeviceToHost, st));
@@ -1690,6 +1930,8 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
         hipLaunchKernelGGL(k6_anchor_final, dim3(ngroups), dim3(256), 0, st, (const Group *)d_groups, d_sorted, d_order,
                            (const unsigned long long *)g_packed.p, (uint2 *)g_anchors.p);
         const bool path = p->anchor_rule == MIMEO_ANCHOR_PATH;
+        const bool bounded = path && p->bound_extensions;   // api.hip: bound_extensions needs the path rule
+        unsigned long long bound_jobs = 0, rescheduled = 0;  // statistics of the bounded mode
         uint64_t pool_budget = 0, arena_used = 0;
         float ms_trace = 0;
         uint32_t trace_slices = 0, rounds = 0;
@@ -1704,6 +1946,7 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
             if ((rc = trace_pool_budget(&pool_budget))) return rc;
             pv = PathView{(const uint2 *)g_pidx.p, nullptr, (uint32_t *)g_accrank.p};
         }
+        if (bounded && (rc = g_sweep.reserve((size_t)nhsps * 2 * sizeof(HalfSweep)))) return rc;
         for (;;) {
             HIP_TRY(hipMemsetAsync(g_cnt.p, 0, 16, st));
             unsigned int *njobs = (unsigned int *)g_cnt.p, *remaining = njobs + 1, *novf = njobs + 2;
@@ -1724,7 +1967,16 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
                 // latter alone; default = the lean single-wavefront kernel (its dead-cell arithmetic needs the
                 // penalties to stay far below 2^29 / 1024)
                 const bool lean_ok = p->gap_extend <= (1 << 16) && p->gap_open <= (1 << 24) && p->ydrop <= (1 << 28);
-                if (lean_ok && !kmode) {
+                const BoundCtx bc{(const mimeo_alignment *)d_aln, (const uint2 *)g_anchors.p, pv};
+                if (bounded) {
+                    // the bounded lean kernel; what does not fit it goes straight to the bounded k6_dp_any
+                    if (lean_ok)
+                        hipLaunchKernelGGL(k6_dp1_bounded, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups, (const DpJob *)g_jobs.p,
+                                           (HalfResult *)g_res.p, (HalfSweep *)g_sweep.p, p->gap_open, p->gap_extend, p->ydrop, bc, novf,
+                                           (unsigned int *)g_ovf_list.p);
+                    else
+                        hipLaunchKernelGGL(k6_list_all, dim3((h[0] + 255) / 256), dim3(256), 0, st, h[0], novf, (unsigned int *)g_ovf_list.p);
+                } else if (lean_ok && !kmode) {
                     hipLaunchKernelGGL(k6_dp1, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups, (const DpJob *)g_jobs.p,
                                        (HalfResult *)g_res.p, p->gap_open, p->gap_extend, p->ydrop);
                 } else {
@@ -1735,9 +1987,10 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
                     hipLaunchKernelGGL(k6_dp, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups, (const DpJob *)g_jobs.p,
                                        (HalfResult *)g_res.p, p->gap_open, p->gap_extend, p->ydrop, use4 ? 1 : 0, cap);
                 }
-                hipLaunchKernelGGL(k6_dp_wide, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups,
-                                   (const DpJob *)g_jobs.p, (HalfResult *)g_res.p, p->gap_open, p->gap_extend, p->ydrop, novf,
-                                   (unsigned int *)g_ovf_list.p, cap);
+                if (!bounded)
+                    hipLaunchKernelGGL(k6_dp_wide, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups,
+                                       (const DpJob *)g_jobs.p, (HalfResult *)g_res.p, p->gap_open, p->gap_extend, p->ydrop, novf,
+                                       (unsigned int *)g_ovf_list.p, cap);
                 // bands beyond 2048 columns (tandem arrays): the global-memory kernel, a few jobs at a time
                 unsigned int nov = 0;
                 HIP_TRY(hipMemcpyAsync(&nov, novf, 4, hipMemcpyDeviceToHost, st));
@@ -1745,10 +1998,16 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
                 if (nov) {
                     const unsigned int slots = std::min<unsigned int>(nov, 32u);
                     if ((rc = g_any.reserve((size_t)slots * ANY_SLOT_WORDS * 4))) return rc;
-                    for (unsigned int f = 0; f < nov; f += slots)
-                        hipLaunchKernelGGL(k6_dp_any, dim3(std::min(slots, nov - f)), dim3(ANY_THREADS), 0, st, (const Group *)d_groups,
-                                           (const DpJob *)g_jobs.p, (const unsigned int *)g_ovf_list.p, f, (HalfResult *)g_res.p,
-                                           (uint32_t *)g_any.p, p->gap_open, p->gap_extend, p->ydrop, cap);
+                    for (unsigned int f = 0; f < nov; f += slots) {
+                        if (bounded)
+                            hipLaunchKernelGGL(k6_dp_any<true>, dim3(std::min(slots, nov - f)), dim3(ANY_THREADS), 0, st, (const Group *)d_groups,
+                                               (const DpJob *)g_jobs.p, (const unsigned int *)g_ovf_list.p, f, (HalfResult *)g_res.p,
+                                               (uint32_t *)g_any.p, p->gap_open, p->gap_extend, p->ydrop, cap, bc, (HalfSweep *)g_sweep.p);
+                        else
+                            hipLaunchKernelGGL(k6_dp_any<false>, dim3(std::min(slots, nov - f)), dim3(ANY_THREADS), 0, st, (const Group *)d_groups,
+                                               (const DpJob *)g_jobs.p, (const unsigned int *)g_ovf_list.p, f, (HalfResult *)g_res.p,
+                                               (uint32_t *)g_any.p, p->gap_open, p->gap_extend, p->ydrop, cap, bc, (HalfSweep *)nullptr);
+                    }
                 }
             }
             if (k6_stats && h[0]) {
@@ -1779,24 +2038,42 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
                 for (auto &r : hr)
                     if (!r.rows && shown < 8) { fprintf(stderr, "  [k6] zero-row job: score %d i %u j %u nm %u nx %u ovf %u\n", r.score, r.i, r.j, r.nm, r.nx, r.overflow); shown++; }
             }
+            if (bounded && k6_stats && h[0]) {   // jobs of the round that met a bound
+                std::vector<DpJob> hj(h[0]);
+                std::vector<HalfSweep> hs((size_t)nhsps * 2);
+                HIP_TRY(hipStreamSynchronize(st));
+                HIP_TRY(hipMemcpy(hj.data(), g_jobs.p, (size_t)h[0] * sizeof(DpJob), hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(hs.data(), g_sweep.p, hs.size() * sizeof(HalfSweep), hipMemcpyDeviceToHost));
+                for (auto &j : hj) bound_jobs += hs[j.slot].nbound ? 1u : 0u;
+            }
             if (path && h[0]) {
                 rounds++;
-                if ((rc = trace_round(d_groups, h[0], p, pool_budget, &arena_used, &ms_trace, &trace_slices, &largest))) return rc;
+                if ((rc = trace_round(d_groups, h[0], p, pool_budget, &arena_used, &ms_trace, &trace_slices, &largest, bounded,
+                                      BoundCtx{(const mimeo_alignment *)d_aln, (const uint2 *)g_anchors.p, pv})))
+                    return rc;
                 pv.blk = (const PathBlock *)g_arena.p;
             }
-            if (path)
+            if (bounded)
+                hipLaunchKernelGGL((k6_resolve<true, true>), dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
+                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv, (const HalfSweep *)g_sweep.p);
+            else if (path)
                 hipLaunchKernelGGL(k6_resolve<true>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv);
+                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv, (const HalfSweep *)nullptr);
             else
                 hipLaunchKernelGGL(k6_resolve<false>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv);
-            HIP_TRY(hipMemcpyAsync(h, g_cnt.p, 8, hipMemcpyDeviceToHost, st));
+                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv, (const HalfSweep *)nullptr);
+            unsigned int h4[4] = {0, 0, 0, 0};
+            HIP_TRY(hipMemcpyAsync(h4, g_cnt.p, 16, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            if (!h[1]) break;
+            rescheduled += h4[3];
+            if (!h4[1]) break;
         }
-        if (path && k6_stats)
-            fprintf(stderr, "[k6] path rule: traceback %.3f ms, rounds %u slices %u, %llu path blocks, pool %.1f MB, largest half %.3f MB\n", ms_trace,
+        if (path && k6_stats) {
+            fprintf(stderr, "[k6] path rule: traceback %.3f ms, rounds %u slices %u, %llu path blocks, pool %.1f MB, largest half %.3f MB", ms_trace,
                     rounds, trace_slices, (unsigned long long)arena_used, g_pool.cap / 1048576.0, largest / 1048576.0);
+            if (bounded) fprintf(stderr, ", bounded jobs %llu, rescheduled %llu", bound_jobs, rescheduled);
+            fprintf(stderr, "\n");
+        }
     }
     hipLaunchKernelGGL(k6_finish, dim3((ngroups + 63) / 64), dim3(64), 0, st, d_groups, ngroups, d_aln, p->hspthresh);
     HIP_TRY(hipGetLastError());

@@ -15,7 +15,7 @@ def mainArgs(argv=None):
     _cli.add_common(parser, 'mimeo-x', 'mimeo_B_in_A.gff3', 'B_Repeat', 'B_Repeat', with_b=True)
     parser.add_argument('--bedtools', type=str, default='bedtools', help='Accepted for compatibility; bedtools is not used.')
     parser.add_argument('--minCov', type=int, default=5, help='Minimum depth of B-genome hits to report feature in A-genome.')
-    return parser.parse_args(argv)
+    return _cli.check_common(parser, parser.parse_args(argv))
 
 
 def main(argv=None):
@@ -32,7 +32,8 @@ def main(argv=None):
     logging.info('Running alignments...')
     workflow.self_repeats(A, pairs, outtab, gffout, minIdt=args.minIdt, minLen=args.minLen, hspthresh=3000,
                           minCov=args.minCov, reuseTab=args.recycle, label=args.label, prefix=args.prefix, dist=dist,
-                          source='mimeo', B=B, anchor_rule=args.anchorRule)
+                          source='mimeo', B=B, anchor_rule=args.anchorRule,
+                          bound_extensions=args.boundExtensions)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

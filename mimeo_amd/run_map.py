@@ -21,7 +21,7 @@ def mainArgs(argv=None):
     parser.add_argument('--maxtandem', type=float, default=None,
                         help='Max percentage of an A-genome alignment which may be masked by TRF.')
     parser.add_argument('--writeTRF', action='store_true', default=False, help='Write TRF-filtered alignment file.')
-    return parser.parse_args(argv)
+    return _cli.check_common(parser, parser.parse_args(argv))
 
 
 def main(argv=None):
@@ -37,7 +37,8 @@ def main(argv=None):
         logging.error('No files to align. Check --adir and --bdir contain at least one fasta each.')
         sys.exit(1)
     workflow.map_hits(A, B, pairs, outtab, minIdt=args.minIdt, minLen=args.minLen, hspthresh=args.hspthresh,
-                      reuseTab=args.recycle, dist=dist, anchor_rule=args.anchorRule)
+                      reuseTab=args.recycle, dist=dist, anchor_rule=args.anchorRule,
+                      bound_extensions=args.boundExtensions)
     if dist.rank == 0:
         logging.info('Importing alignments from %s' % outtab)
         rows = formats.parse_tab(outtab)

@@ -17,7 +17,7 @@ def mainArgs(argv=None):
                         help='Minimum depth of aligned segments from same scaffold to report feature. Used if "--strictSelf" mode is selected.')
     parser.add_argument('--strictSelf', action='store_true',
                         help='If set process same-scaffold alignments separately with option to use higher "--intraCov" threshold.')
-    return parser.parse_args(argv)
+    return _cli.check_common(parser, parser.parse_args(argv))
 
 
 def main(argv=None):
@@ -34,7 +34,7 @@ def main(argv=None):
     workflow.self_repeats(A, pairs, outtab, gffout, minIdt=args.minIdt, minLen=args.minLen, hspthresh=args.hspthresh,
                           minCov=args.minCov, intraCov=args.intraCov, splitSelf=args.strictSelf, reuseTab=args.recycle,
                           label=args.label, prefix=args.prefix, dist=dist,
-                          anchor_rule=args.anchorRule)
+                          anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

@@ -123,6 +123,44 @@ def tandem_genome(seed, nscaf, scaf_bp, per_scaffold=3, repeat_frac=0.05, famili
     return names, add_tandem_arrays(seed, arrs, per_scaffold)
 
 
+def flanked_tandem_genome(seed, nscaf, flank=20000, unit=(40, 280), copies=(10, 40), pad=2000, flank_div=0.015, flank_indels=4,
+                          copy_div=0.1, delta=5, array_indels=6):
+    """Scaffolds that share two unique flanks around a short-unit tandem array: pad | diverged copy of flank 1 | array of
+    the scaffold's own copy number | diverged copy of flank 2 | pad.  The array derives from a run of n + delta diverged
+    copies (up to `copy_div` substitutions each) of one unit of `unit` bp, n drawn from `copies`; every scaffold loses up
+    to 2 delta of them at random places, so that two scaffolds' copy numbers differ by -delta .. +delta around n.  Flanks
+    and array carry `flank_div` substitutions per scaffold and `flank_indels` / `array_indels` indels of 1-3 bases.  A gap
+    of g bases costs 400 + 30 g against y-drop 9400, so with units below ~300 bp a gapped extension can shift register
+    inside the array: under the path anchor rule the chained anchors of the array that the first alignment passed on
+    another register are accepted, and each one's extension leaves the array along the flanks unless extensions are
+    bounded by the earlier alignments (mimeo_params.bound_extensions; DESIGN.md §2 rule 7).  Deterministic in `seed`.
+    Returns (names, uint8 ASCII arrays)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    f1 = rng.integers(0, 4, size=flank, dtype=np.uint8)
+    f2 = rng.integers(0, 4, size=flank, dtype=np.uint8)
+    u = rng.integers(0, 4, size=int(rng.integers(unit[0], unit[1] + 1)), dtype=np.uint8)
+    n0 = int(rng.integers(copies[0], copies[1] + 1))
+
+    def diverged(c, div, nindel):
+        c = c.copy()
+        m = rng.random(c.size) < div
+        c[m] = (c[m] + rng.integers(1, 4, size=int(m.sum()), dtype=np.uint8)) & 3
+        for p in sorted(rng.integers(100, max(101, c.size - 100), size=nindel).tolist(), reverse=True):
+            ln = int(rng.integers(1, 4))
+            c = np.delete(c, slice(p, p + ln)) if rng.random() < 0.5 else np.insert(c, p, rng.integers(0, 4, size=ln, dtype=np.uint8))
+        return c
+
+    master = [diverged(u, float(rng.random()) * copy_div, 0) for _ in range(n0 + delta)]
+    seqs = []
+    for _ in range(nscaf):
+        keep = np.sort(rng.permutation(len(master))[:max(2, len(master) - int(rng.integers(0, 2 * delta + 1)))])
+        arr = diverged(np.concatenate([master[k] for k in keep]), flank_div, array_indels)
+        parts = [rng.integers(0, 4, size=pad, dtype=np.uint8), diverged(f1, flank_div, flank_indels), arr,
+                 diverged(f2, flank_div, flank_indels), rng.integers(0, 4, size=pad, dtype=np.uint8)]
+        seqs.append(_ACGT[np.concatenate(parts)])
+    return ['flk%04d' % i for i in range(nscaf)], seqs
+
+
 def write_fasta(path, names, seqs, width=60):
     with open(path, 'wb') as f:
         for n, s in zip(names, seqs):

@@ -33,6 +33,14 @@ def anchor_rule_code(rule):
     return int(rule)
 
 
+def gapped_params(hspthresh, anchor_rule, bound_extensions):
+    """engine parameters of a workflow: --hspthresh, --anchorRule, --boundExtensions (only with the path rule)"""
+    rule = anchor_rule_code(anchor_rule)
+    if bound_extensions and rule != engine._ffi.ANCHOR_PATH:
+        raise ValueError('bound_extensions needs the path anchor rule (anchor_rule=%r)' % (anchor_rule,))
+    return engine.default_params(hspthresh=hspthresh, anchor_rule=rule, bound_extensions=1 if bound_extensions else 0)
+
+
 PACK_MEMBER_BP = 6 << 20   # the engine packs scaffolds of up to this size into super-scaffolds when there are at least ...
 PACK_MIN = 8               # ... this many of them (mimeo_hip.h, mimeo_align_pairs)
 
@@ -109,14 +117,15 @@ def collapse_to_gff(tab_path, names, lengths, min_cov, min_len, source, label, p
 
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
-                 B=None, anchor_rule='box'):
+                 B=None, anchor_rule='box', bound_extensions=False):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  anchor_rule: the gapped stage's skip rule, 'box' or
-    'path' (or its _ffi.ANCHOR_* number; mimeo_hip.h MIMEO_ANCHOR_*)."""
+    'path' (or its _ffi.ANCHOR_* number; mimeo_hip.h MIMEO_ANCHOR_*).  bound_extensions: bound every gapped extension by
+    the earlier alignments of its pair and strand (mimeo_params.bound_extensions); ValueError without the path rule."""
     dist = dist or Dist()
     outtab_intra = outtab + '_intra.tab'
     kept = None
     if not reuseTab or not os.path.isfile(outtab):
-        params = engine.default_params(hspthresh=hspthresh, anchor_rule=anchor_rule_code(anchor_rule))
+        params = gapped_params(hspthresh, anchor_rule, bound_extensions)
         blocks, _, kept = align_blocks(A, B, pairs, params, minLen, minIdt, dist)
         if len(set(pairs)) != len(pairs):
             kept = None   # a pair listed twice is written twice (the reference would run it twice): read the file back instead
@@ -149,11 +158,13 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     return lines
 
 
-def map_hits(A, B, pairs, outtab, minIdt=95, minLen=100, hspthresh=3000, reuseTab=False, dist=None, anchor_rule='box'):
-    """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse.  anchor_rule as self_repeats."""
+def map_hits(A, B, pairs, outtab, minIdt=95, minLen=100, hspthresh=3000, reuseTab=False, dist=None, anchor_rule='box',
+             bound_extensions=False):
+    """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse.  anchor_rule and bound_extensions
+    as self_repeats."""
     dist = dist or Dist()
     if not reuseTab or not os.path.isfile(outtab):
-        params = engine.default_params(hspthresh=hspthresh, anchor_rule=anchor_rule_code(anchor_rule))
+        params = gapped_params(hspthresh, anchor_rule, bound_extensions)
         blocks, _, _ = align_blocks(A, B, pairs, params, minLen, minIdt, dist)
         if dist.rank == 0:
             write_tab(outtab, pairs, blocks)
