@@ -206,10 +206,6 @@ static int check_params(const mimeo_params *p) {
         set_error("bound_extensions needs anchor_rule = MIMEO_ANCHOR_PATH (1)");
         return MIMEO_ERR_ARG;
     }
-    if (p->bound_extensions && getenv("MIMEO_K6_KERNEL")) {
-        set_error("bound_extensions: the development kernels of MIMEO_K6_KERNEL have no bounded form");
-        return MIMEO_ERR_ARG;
-    }
     return 0;
 }
 

@@ -5,18 +5,23 @@
 // (gap open 400 / extend 30, y-drop 9400) and the two halves are joined.
 //
 // Decomposition:
-//   * a half extension is one JOB executed by one wavefront.  The DP is evaluated row by row;
-//     lane l owns the 16-column strip (j / 16) % 64 == l of a 1024-column window that slides with
-//     the first live column, all state (score + match/mismatch counts of the C and D planes) in
-//     registers.  Inside a row the only horizontal dependency is the insertion state, computed
-//     as a max-plus prefix scan of u_k = H_k + k*E (in-lane over the strip, then one cross-lane
-//     scan).  Pruning: a cell scoring below (best of the rows above) - ydrop is dead.  Cells carry
-//     (score, matches, mismatches), so identity needs no traceback.
-//   * exact shortcut: if the two sequences are identical and N-free from the anchor to the end of
-//     the shorter one, the diagonal is optimal (every column already scores its maximum) and the
-//     DP is skipped — this is what makes the trivial (A,A) self alignment cheap.
+//   * a half extension is one JOB.  The DP is evaluated row by row; pruning: a cell scoring below
+//     (best of the rows above) - ydrop is dead.  Cells carry (score, matches, mismatches), so
+//     identity needs no traceback.  Inside a row the only horizontal dependency is the insertion
+//     state, a max-plus prefix scan along the row (in-lane over a strip, then one cross-lane scan).
+//     Three kernels, each taking the jobs the one before could not hold (dp_round):
+//       - k6_dp1, the lean kernel: one wavefront, lane l owns the 14-column strip (j / 14) % 64 == l
+//         of an 896-column window that slides with the first live column, all state in registers,
+//         counts packed into 16 bits each (65 535 rows at most);
+//       - k6_dp_wide, the second chance: the same layout with 32-column strips (2048 columns),
+//         unpacked counts and no row limit;
+//       - k6_dp_any, the last resort: one workgroup, the rows in global memory, bands up to 2^16
+//         columns, cells rebased when the score nears 2^31.
+//   * exact shortcut (identical_suffix): if the two sequences are identical and N-free from the
+//     anchor to the end of the shorter one, the diagonal is optimal (every column already scores its
+//     maximum) and the DP is skipped — this is what makes the trivial (A,A) self alignment cheap.
 //   * jobs of different anchors are independent, only the skip rule is ordered: each round takes
-//     the next <= nbatch unskipped anchors of every group (k6_pick), extends them all (k6_dp),
+//     the next <= nbatch unskipped anchors of every group (k6_pick), extends them all (dp_round),
 //     then replays the skip rule in order over the batch (k6_resolve).
 //   * path rule (mimeo_params.anchor_rule = MIMEO_ANCHOR_PATH, opt-in): an anchor is skipped iff it is a diagonal step of
 //     the path of an earlier alignment.  After a round's DP kernels k6_trace re-runs the round's halves with a traceback,
@@ -29,7 +34,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "device_util.h"
@@ -38,7 +42,7 @@ namespace mimeo {
 
 constexpr int32_t NEG = -(1 << 30);
 constexpr int32_t NEGH = -(1 << 29);
-// columns per lane: 16 (1024-column window) in k6_dp, 32 (2048 columns) in the second-chance kernel
+// columns per lane: 14 (896-column window) in the lean kernel k6_dp1, 32 (2048 columns) in the second-chance kernel
 
 struct Cell {
     int32_t s;
@@ -119,7 +123,7 @@ __device__ __forceinline__ Best4 wave_best(Best4 v) {
 template <int WSTRIP>
 __device__ __forceinline__ void load_qbits(const GStrandView &Q, uint32_t aq, int dir, uint32_t jb, uint32_t lenB,
                                            uint32_t &qlo, uint32_t &qhi, uint32_t &qn) {
-    constexpr uint32_t SMASK = WSTRIP == 32 ? 0xFFFFFFFFu : ((1u << (WSTRIP & 31)) - 1u);  // WSTRIP in {4, 16, 32}
+    constexpr uint32_t SMASK = WSTRIP == 32 ? 0xFFFFFFFFu : ((1u << (WSTRIP & 31)) - 1u);  // WSTRIP in {14, 32}
     if (jb > lenB) { qlo = qhi = qn = 0; return; }
     if (dir > 0) {
         int32_t p = (int32_t)(aq + jb) - 1;
@@ -134,7 +138,6 @@ __device__ __forceinline__ void load_qbits(const GStrandView &Q, uint32_t aq, in
     }
 }
 
-// One-sided y-drop affine extension by one wavefront (all lanes return the same result).
 // Target bases of 32 consecutive DP rows i0 .. i0+31 (bit b <-> row i0 + b): one window load per 32 rows
 // instead of a dependent global load in every row; the caller fetches one block ahead.
 struct RowBases { uint32_t lo, hi, nm; };
@@ -147,42 +150,44 @@ __device__ __forceinline__ RowBases load_row_bases(const GStrandView &T, uint32_
     return RowBases{__brev(w.lo), __brev(w.hi), __brev(w.nm)};
 }
 
-template <int WSTRIP>
-__device__ HalfResult wave_half_extend(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir,
-                                       int32_t O, int32_t E, int32_t Y, int32_t cap) {
-    constexpr int WINDOW = 64 * WSTRIP;  // columns in the sliding window
-    constexpr int WSHIFT = WSTRIP == 32 ? 5 : 4;
-    static_assert((1 << WSHIFT) == WSTRIP, "WSTRIP must be 16 or 32");
+// The exact shortcut of a half extension, by one wavefront (every lane returns the same): true, and the result in `out`, iff
+// the two sequences are identical and N-free from the anchor to the end of the shorter one (n bases); `out` is untouched
+// otherwise.  The result is the diagonal: i == j == nm == n, and rows == 0 marks it as a shortcut result whose score is
+// 64 bits wide, low word in score, high word in maxcols (half_score; k6_trace's TR_DIAG).
+__device__ bool identical_suffix(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir, HalfResult &out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n = min(dir > 0 ? T.len - at : at, dir > 0 ? Q.len - aq : aq);
+    const int32_t st = dir > 0 ? (int32_t)at : (int32_t)(at - n), sq = dir > 0 ? (int32_t)aq : (int32_t)(aq - n);
+    bool ok = true;
+    uint64_t ncg = 0;
+    for (uint32_t k0 = 0; k0 < n; k0 += 64u * 32u) {
+        uint32_t k = k0 + lane * 32u;
+        if (k < n) {
+            const Win32 tw = win32(T, st + (int32_t)k), qw = win32(Q, sq + (int32_t)k);
+            uint32_t bad = (tw.lo ^ qw.lo) | (tw.hi ^ qw.hi) | tw.nm | qw.nm;
+            uint32_t rem = n - k, mask = rem < 32 ? (1u << rem) - 1u : 0xFFFFFFFFu;
+            if (bad & mask) ok = false;
+            ncg += __popc((tw.lo ^ tw.hi) & mask);
+        }
+        if (__ballot(!ok)) break;
+    }
+    if (__ballot(!ok)) return false;
+    for (int o = 32; o > 0; o >>= 1) ncg += __shfl_xor(ncg, o);
+    const uint64_t sc = 100ull * ncg + 91ull * ((uint64_t)n - ncg);
+    out.score = (int32_t)(uint32_t)sc; out.maxcols = (uint32_t)(sc >> 32); out.i = n; out.j = n; out.nm = n; out.nx = 0;
+    return true;
+}
+
+// The 2048-column kernel: one-sided y-drop affine extension by one wavefront (all lanes return the same result), 32 columns
+// per lane, unpacked counts, no limit on the rows.
+__device__ HalfResult wave_half_extend_2048(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir,
+                                            int32_t O, int32_t E, int32_t Y, int32_t cap) {
+    constexpr int WSTRIP = 32, WINDOW = 64 * WSTRIP;  // columns per lane, columns in the sliding window
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t lenA = dir > 0 ? T.len - at : at, lenB = dir > 0 ? Q.len - aq : aq;
     HalfResult best{0, 0, 0, 0, 0, 0, 0, 0};
-    // ---- exact shortcut: identical, N-free to the end of the shorter sequence
-    {
-        const uint32_t n = min(lenA, lenB);
-        const int32_t st = dir > 0 ? (int32_t)at : (int32_t)(at - n), sq = dir > 0 ? (int32_t)aq : (int32_t)(aq - n);
-        bool ok = true;
-        uint64_t ncg = 0;
-        for (uint32_t k0 = 0; k0 < n; k0 += 64u * 32u) {
-            uint32_t k = k0 + lane * 32u;
-            if (k < n) {
-                const Win32 tw = win32(T, st + (int32_t)k), qw = win32(Q, sq + (int32_t)k);
-                const uint32_t tlo = tw.lo, thi = tw.hi;
-                uint32_t bad = (tlo ^ qw.lo) | (thi ^ qw.hi) | tw.nm | qw.nm;
-                uint32_t rem = n - k, mask = rem < 32 ? (1u << rem) - 1u : 0xFFFFFFFFu;
-                if (bad & mask) ok = false;
-                ncg += __popc((tlo ^ thi) & mask);
-            }
-            if (__ballot(!ok)) break;
-        }
-        if (!__ballot(!ok)) {
-            for (int o = 32; o > 0; o >>= 1) ncg += __shfl_xor(ncg, o);
-            uint64_t sc = 100ull * ncg + 91ull * ((uint64_t)n - ncg);
-            // rows == 0 marks a shortcut result: its score is 64 bits wide, high word in maxcols (k6_resolve)
-            best.score = (int32_t)(uint32_t)sc; best.maxcols = (uint32_t)(sc >> 32); best.i = n; best.j = n; best.nm = n; best.nx = 0;
-            return best;
-        }
-    }
-    // ---- general row-by-row DP.  Lane l owns columns wb + 16*l .. wb + 16*l + 15 (rank == lane); when
+    if (identical_suffix(T, Q, at, aq, dir, best)) return best;
+    // ---- general row-by-row DP.  Lane l owns columns wb + 32*l .. wb + 32*l + 31 (rank == lane); when
     // the first live column crosses a strip boundary the whole state moves down by that many lanes.
     int32_t Cs[WSTRIP], Ds[WSTRIP];
     uint32_t Cm[WSTRIP], Cx[WSTRIP], Dm[WSTRIP], Dx[WSTRIP];
@@ -279,7 +284,7 @@ __device__ HalfResult wave_half_extend(const GStrandView &T, const GStrandView &
         const uint32_t plo = wb + rf * WSTRIP + (uint32_t)__builtin_ctz(fmask);
         const uint32_t nwb = plo & ~(uint32_t)(WSTRIP - 1);
         if (nwb != wb) {
-            const uint32_t shift = (nwb - wb) >> WSHIFT;  // == rf
+            const uint32_t shift = (nwb - wb) / WSTRIP;  // == rf
             wb = nwb;
             jb = wb + lane * WSTRIP;
             const int src = (int)((lane + shift) & 63u);
@@ -295,249 +300,6 @@ __device__ HalfResult wave_half_extend(const GStrandView &T, const GStrandView &
             uint32_t a0 = __shfl(qlo, src), a1 = __shfl(qhi, src), a2 = __shfl(qn, src);
             if (fresh) load_qbits<WSTRIP>(Q, aq, dir, jb, lenB, qlo, qhi, qn);
             else { qlo = a0; qhi = a1; qn = a2; }
-        }
-    }
-    return best;
-}
-
-// ---- four-wavefront variant of the same DP -----------------------------------------------------
-// One workgroup of four wavefronts (one per SIMD) shares a half extension: wavefront of rank r owns
-// the 256 columns wb + 256 r ..., four per lane.  The row costs each wavefront a quarter of the
-// VALU work of the single-wavefront kernel plus two workgroup barriers, so a half extension finishes
-// ~3-4x sooner — which is what matters when a K6 round has fewer jobs than the chip has SIMDs
-// (multi-GPU shards, last rounds).  The window slides in whole 256-column blocks (the ring of four
-// wavefronts rotates, no state moves), so only 769 columns are guaranteed; a band that does not fit
-// is redone by the single-wavefront kernels.
-constexpr int C4_WS = 4, C4_WCOLS = 64 * C4_WS, C4_THREADS = 256;
-
-// k6_dp4 carries (matches, mismatches) packed into one word, 16 bits each: a third less to select, scan and
-// exchange per cell.  Counts grow by one per row at most, so rows < 65535 cannot overflow them; longer half
-// extensions fall back to the single-wavefront kernels (unpacked).
-struct PCell {
-    int32_t s;
-    uint32_t c;  // matches | mismatches << 16
-};
-struct PBest {
-    int32_t s;
-    uint32_t j, c;
-};
-__device__ __forceinline__ PCell pcmax_left(const PCell &l, const PCell &r) { return r.s > l.s ? r : l; }
-template <int CTRL, int RMASK>
-__device__ __forceinline__ PCell dpp_pcell(const PCell &c) {
-    PCell o;
-    o.s = __builtin_amdgcn_update_dpp(NEG, c.s, CTRL, RMASK, 0xf, false);
-    o.c = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c.c, CTRL, RMASK, 0xf, false);
-    return o;
-}
-__device__ __forceinline__ PCell wave_incl_maxscan_p(PCell v) {
-    v = pcmax_left(dpp_pcell<0x111, 0xf>(v), v);
-    v = pcmax_left(dpp_pcell<0x112, 0xf>(v), v);
-    v = pcmax_left(dpp_pcell<0x114, 0xf>(v), v);
-    v = pcmax_left(dpp_pcell<0x118, 0xf>(v), v);
-    v = pcmax_left(dpp_pcell<0x142, 0xa>(v), v);
-    v = pcmax_left(dpp_pcell<0x143, 0xc>(v), v);
-    return v;
-}
-template <int CTRL, int RMASK>
-__device__ __forceinline__ PBest dpp_pbest(const PBest &c) {
-    PBest o;
-    o.s = __builtin_amdgcn_update_dpp(NEG, c.s, CTRL, RMASK, 0xf, false);
-    o.j = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c.j, CTRL, RMASK, 0xf, false);
-    o.c = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c.c, CTRL, RMASK, 0xf, false);
-    return o;
-}
-__device__ __forceinline__ PBest pbmax_left(const PBest &l, const PBest &r) { return r.s > l.s ? r : l; }
-__device__ __forceinline__ PBest wave_best_p(PBest v) {
-    v = pbmax_left(dpp_pbest<0x111, 0xf>(v), v);
-    v = pbmax_left(dpp_pbest<0x112, 0xf>(v), v);
-    v = pbmax_left(dpp_pbest<0x114, 0xf>(v), v);
-    v = pbmax_left(dpp_pbest<0x118, 0xf>(v), v);
-    v = pbmax_left(dpp_pbest<0x142, 0xa>(v), v);
-    v = pbmax_left(dpp_pbest<0x143, 0xc>(v), v);
-    PBest t;
-    t.s = __builtin_amdgcn_readlane(v.s, 63); t.j = (uint32_t)__builtin_amdgcn_readlane((int)v.j, 63);
-    t.c = (uint32_t)__builtin_amdgcn_readlane((int)v.c, 63);
-    return t;
-}
-
-struct C4Shared {
-    PCell bnd[2][4];  // [row parity][wavefront]: C of the wavefront's last column
-    PCell tot[4];     // per-wavefront maximum of u
-    uint32_t first[4], last[4];
-    PBest best[4];
-    int flag;
-};
-
-__device__ HalfResult block_half_extend(C4Shared &sh, const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq,
-                                        int dir, int32_t O, int32_t E, int32_t Y) {
-    constexpr int WS = C4_WS;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t lenA = dir > 0 ? T.len - at : at, lenB = dir > 0 ? Q.len - aq : aq;
-    HalfResult best{0, 0, 0, 0, 0, 0, 0, 0};
-    // ---- exact shortcut: identical, N-free to the end of the shorter sequence
-    {
-        const uint32_t n = min(lenA, lenB);
-        const int32_t st = dir > 0 ? (int32_t)at : (int32_t)(at - n), sq = dir > 0 ? (int32_t)aq : (int32_t)(aq - n);
-        bool ok = true;
-        uint32_t ncg = 0;
-        for (uint32_t k0 = 0; k0 < n; k0 += C4_THREADS * 32u) {
-            uint32_t k = k0 + tid * 32u;
-            if (k < n) {
-                const Win32 tw = win32(T, st + (int32_t)k), qw = win32(Q, sq + (int32_t)k);
-                uint32_t bad = (tw.lo ^ qw.lo) | (tw.hi ^ qw.hi) | tw.nm | qw.nm;
-                uint32_t rem = n - k, mask = rem < 32 ? (1u << rem) - 1u : 0xFFFFFFFFu;
-                if (bad & mask) ok = false;
-                ncg += __popc((tw.lo ^ tw.hi) & mask);
-            }
-            if (__syncthreads_or(!ok)) { ok = false; break; }
-        }
-        if (!__syncthreads_or(!ok)) {
-            // block sum of ncg through the shared scratch (64-bit total)
-            unsigned long long tsum = ncg;
-            for (int o = 32; o > 0; o >>= 1) tsum += __shfl_xor(tsum, o);
-            if (lane == 0) { sh.first[wave] = (uint32_t)tsum; sh.last[wave] = (uint32_t)(tsum >> 32); }
-            __syncthreads();
-            unsigned long long all = 0;
-            for (int w = 0; w < 4; w++) all += ((unsigned long long)sh.last[w] << 32) | sh.first[w];
-            __syncthreads();
-            unsigned long long sc = 100ull * all + 91ull * ((unsigned long long)n - all);
-            // rows == 0 marks a shortcut result: its score is 64 bits wide, high word in maxcols (k6_resolve)
-            best.score = (int32_t)(uint32_t)sc; best.maxcols = (uint32_t)(sc >> 32); best.i = n; best.j = n; best.nm = n; best.nx = 0;
-            return best;
-        }
-    }
-    // ---- row-by-row DP
-    int32_t Cs[WS], Ds[WS];
-    uint32_t Cc[WS], Dc[WS];  // matches | mismatches << 16 (PCell)
-    uint32_t wb = 0, wbase = 0;                      // window base column (multiple of 256), wavefront holding it
-    uint32_t rw = wave, jb = rw * C4_WCOLS + lane * WS;  // my rank in the ring, my first column
-    uint32_t qlo, qhi, qn;
-    load_qbits<WS>(Q, aq, dir, jb, lenB, qlo, qhi, qn);
-#pragma unroll
-    for (int s = 0; s < WS; s++) {
-        uint32_t j = jb + s;
-        int32_t v = j ? -O - (int32_t)j * E : 0;
-        bool alive = j <= lenB && (j == 0 || v >= -Y);
-        Cs[s] = alive ? v : NEG; Cc[s] = 0;
-        Ds[s] = NEG; Dc[s] = 0;
-    }
-    {   // row 0 must fit the guaranteed part of the window
-        uint32_t hi0 = 0;
-        if (Y >= O + E) hi0 = min(lenB, (uint32_t)((Y - O) / E));
-        if (hi0 >= 4 * C4_WCOLS - WS) { best.overflow = 1; return best; }
-    }
-    if (lane == 63) sh.bnd[0][wave] = PCell{Cs[WS - 1], 0};
-    __syncthreads();
-    uint32_t par = 0;
-    RowBases rbase{0, 0, 0}, rnext = load_row_bases(T, at, dir, 1u);
-    for (uint32_t i = 1; i <= lenA; i++, par ^= 1u) {
-        // the packed counts hold 16 bits each: a longer extension is redone by the single-wavefront kernel
-        if (i >= 0xFFFFu) { best.overflow = 1; break; }
-        const int32_t thr = best.score - Y;
-        const uint32_t rbit = (i - 1u) & 31u;
-        if (rbit == 0) { rbase = rnext; rnext = load_row_bases(T, at, dir, i + 32u); }
-        const uint32_t alo = (rbase.lo >> rbit) & 1u, ahi = (rbase.hi >> rbit) & 1u, an = (rbase.nm >> rbit) & 1u, acg = alo ^ ahi;
-        // C of the column left of my strip (previous row)
-        PCell p7 = dpp_pcell<0x138, 0xf>(PCell{Cs[WS - 1], Cc[WS - 1]});
-        if (lane == 0) p7 = rw ? sh.bnd[par][(wave + 3u) & 3u] : PCell{NEG, 0};
-#pragma unroll
-        for (int s = WS - 1; s >= 0; s--) {
-            const uint32_t j = jb + s;
-            const bool exists = j <= lenB;
-            PCell dd{NEG, 0}, g{NEG, 0};
-            if (Ds[s] > NEGH) { dd.s = Ds[s] - E; dd.c = Dc[s]; }
-            if (Cs[s] > NEGH && Cs[s] - O - E > dd.s) { dd.s = Cs[s] - O - E; dd.c = Cc[s]; }
-            PCell pc = s ? PCell{Cs[s ? s - 1 : 0], Cc[s ? s - 1 : 0]} : p7;
-            if (pc.s > NEGH && j >= 1) {
-                uint32_t dl = alo ^ ((qlo >> s) & 1u), dh = ahi ^ ((qhi >> s) & 1u), nn = an | ((qn >> s) & 1u);
-                bool m = !(dl | dh | nn);
-                g.s = pc.s + sub_score(dl, dh, acg, nn);
-                g.c = pc.c + (m ? 1u : 0x10000u);
-            }
-            if (!exists) { dd.s = NEG; g.s = NEG; }
-            Ds[s] = dd.s; Dc[s] = dd.c;
-            PCell hh = g;
-            if (dd.s > g.s) hh = dd;
-            Cs[s] = hh.s; Cc[s] = hh.c;
-        }
-        // insertion state: u_k = H_k + (k - wb) * E; in-lane, in-wavefront (DPP), across wavefronts (LDS)
-        const int32_t koff = (int32_t)(rw * C4_WCOLS + lane * WS);
-        PCell run{NEG, 0};
-#pragma unroll
-        for (int s = 0; s < WS; s++) {
-            PCell u{Cs[s] > NEGH ? Cs[s] + (koff + s) * E : NEG, Cc[s]};
-            run = pcmax_left(run, u);
-        }
-        const PCell inc = wave_incl_maxscan_p(run);
-        if (lane == 63) sh.tot[wave] = inc;
-        __syncthreads();
-        PCell acc{NEG, 0};
-        for (uint32_t r = 0; r < rw; r++) acc = pcmax_left(acc, sh.tot[(wbase + r) & 3u]);
-        acc = pcmax_left(acc, dpp_pcell<0x138, 0xf>(inc));
-        uint32_t amask = 0;
-        PBest rb{NEG, 0xFFFFFFFFu, 0};
-#pragma unroll
-        for (int s = 0; s < WS; s++) {
-            PCell hh{Cs[s], Cc[s]};
-            PCell I{NEG, acc.c};
-            if (acc.s > NEGH) I.s = acc.s - O - (koff + s) * E;
-            PCell u{hh.s > NEGH ? hh.s + (koff + s) * E : NEG, hh.c};
-            acc = pcmax_left(acc, u);
-            PCell c = hh;
-            if (I.s > c.s) c = I;
-            const bool alive = (jb + s <= lenB) && c.s >= thr && c.s > NEGH;
-            Cs[s] = alive ? c.s : NEG; Cc[s] = c.c;
-            if (!alive) Ds[s] = NEG;
-            if (alive) {
-                amask |= 1u << s;
-                if (c.s > rb.s) { rb.s = c.s; rb.j = jb + s; rb.c = c.c; }
-            }
-        }
-        // publish: boundary cell for the next row, first / last live column, best cell
-        if (lane == 63) sh.bnd[par ^ 1u][wave] = PCell{Cs[WS - 1], Cc[WS - 1]};
-        const uint64_t ball = __ballot(amask != 0);
-        uint32_t wfirst = 0xFFFFFFFFu, wlast = 0;
-        if (ball) {
-            const uint32_t lf = (uint32_t)__builtin_ctzll(ball), ll = 63u - (uint32_t)__builtin_clzll(ball);
-            const uint32_t mf = (uint32_t)__builtin_amdgcn_readlane((int)amask, (int)lf);
-            const uint32_t ml = (uint32_t)__builtin_amdgcn_readlane((int)amask, (int)ll);
-            const uint32_t cb = wb + rw * C4_WCOLS;
-            wfirst = cb + lf * WS + (uint32_t)__builtin_ctz(mf);
-            wlast = cb + ll * WS + (31u - (uint32_t)__builtin_clz(ml));
-        }
-        PBest wbest{NEG, 0xFFFFFFFFu, 0};
-        if (__ballot(rb.s > best.score)) wbest = wave_best_p(rb);
-        if (lane == 0) { sh.first[wave] = wfirst; sh.last[wave] = wlast; sh.best[wave] = wbest; }
-        __syncthreads();
-        uint32_t first = 0xFFFFFFFFu, last = 0;
-        PBest tb{NEG, 0xFFFFFFFFu, 0};
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            first = min(first, sh.first[w]);
-            last = max(last, sh.last[w]);
-            const PBest o = sh.best[w];
-            if (o.s > tb.s || (o.s == tb.s && o.j < tb.j)) tb = o;
-        }
-        if (first == 0xFFFFFFFFu) break;
-        if (last - wb >= 4 * C4_WCOLS - WS) { best.overflow = 1; break; }
-        best.maxcols = max(best.maxcols, last - wb + 1);
-        best.rows = i;
-        if (tb.s > best.score) { best.score = tb.s; best.i = i; best.j = tb.j; best.nm = tb.c & 0xFFFFu; best.nx = tb.c >> 16; }
-        // slide the window by whole 256-column blocks: the ring of wavefronts rotates
-        const uint32_t k = (first - wb) / C4_WCOLS;
-        if (k) {
-            const bool fresh = rw < k;  // my block left the window: I re-enter on the right with new columns
-            wb += k * C4_WCOLS;
-            wbase = (wbase + k) & 3u;
-            rw = (wave - wbase) & 3u;
-            jb = wb + rw * C4_WCOLS + lane * WS;
-            if (fresh) {
-#pragma unroll
-                for (int s = 0; s < WS; s++) { Cs[s] = NEG; Ds[s] = NEG; }
-                load_qbits<WS>(Q, aq, dir, jb, lenB, qlo, qhi, qn);
-                if (lane == 63) sh.bnd[par ^ 1u][wave] = PCell{NEG, 0};
-            }
-            __syncthreads();
         }
     }
     return best;
@@ -648,17 +410,19 @@ __device__ __forceinline__ bool bounds_none(const BoundCtx &B, uint64_t b0, uint
 }
 
 // ---- lean single-wavefront DP (k6_dp1): the production kernel -----------------------------------------------
-// Same recurrences, pruning and tie-breaks as wave_half_extend<16> (one wavefront, 16 columns per lane, 1024-column
-// window that slides by whole strips), written for VALU issue, which is what bounds K6 (profiles/r02_*: both
-// older kernels spend 1700+ issue slots per DP row):
-//   * counts packed (matches | mismatches << 16): one select instead of two;
+// Same recurrences, pruning and tie-breaks as wave_half_extend_2048 (one wavefront, a strip of columns per lane, a window
+// that slides by whole strips), written for VALU issue, which is what bounds K6 (profiles/r02_*: that kernel's form spent
+// 1700+ issue slots per DP row at 16 columns per lane):
+//   * counts packed into one word (PCell), 16 bits each: one select instead of two, a third less to scan and exchange
+//     per cell.  They grow by one per row at most, so rows < 65535 cannot overflow them; a longer half extension is redone
+//     by the 2048-column kernel (unpacked);
 //   * no liveness guards: a dead cell is any value below NEGH, arithmetic on it stays below NEGH for the one row
 //     until pruning resets it to NEG, so max / compare need no special cases;
 //   * the substitution score of a cell is ONE v_perm_b32: the row's target base is wave-uniform, so the four
 //     possible scores (+128, as bytes) sit in a scalar register and the column's query base is a precomputed byte
 //     selector (selector 4 = the constant 28 = -100 + 128 of an N column; an N row is the table 0x1C1C1C1C);
 //   * the insertion state is carried in the frame of the current column (acc = max(acc, H) - E) instead of
-//     u_k = H_k + k E: no per-column constants; lanes are stitched with one max-scan of (aggregate + lane * 16 E);
+//     u_k = H_k + k E: no per-column constants; lanes are stitched with one max-scan of (aggregate + lane * 14 E);
 //   * per cell the row maximum is one v_max; which cell it was (smallest column on ties) is found with scalar
 //     reads only in rows that improve the best score; liveness is per strip (row maximum above NEGH), which is
 //     all the window slide and the overflow test ever needed;
@@ -672,6 +436,19 @@ struct LeanState {
     int32_t C[L_WS], D[L_WS];
     uint32_t Cc[L_WS], Dc[L_WS], sel[L_WS];
 };
+// a cell of the lean kernel as it moves between lanes: score and packed counts (matches | diagonal steps << 16)
+struct PCell {
+    int32_t s;
+    uint32_t c;
+};
+__device__ __forceinline__ PCell pcmax_left(const PCell &l, const PCell &r) { return r.s > l.s ? r : l; }  // ties -> left
+template <int CTRL, int RMASK>
+__device__ __forceinline__ PCell dpp_pcell(const PCell &c) {
+    PCell o;  // lanes without a valid source keep the identity (NEG, 0), as dpp_cell
+    o.s = __builtin_amdgcn_update_dpp(NEG, c.s, CTRL, RMASK, 0xf, false);
+    o.c = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c.c, CTRL, RMASK, 0xf, false);
+    return o;
+}
 
 __device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
     v = max(v, __builtin_amdgcn_update_dpp(INT32_MIN, v, 0x111, 0xf, 0xf, false));
@@ -778,31 +555,8 @@ __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandV
     const uint32_t lenA = dir > 0 ? T.len - at : at, lenB = dir > 0 ? Q.len - aq : aq;
     HalfResult best{0, 0, 0, 0, 0, 0, 0, 0};
     if (BOUND) *sw = HalfSweep{0, 0, nacc, 0};
-    // ---- exact shortcut: identical, N-free to the end of the shorter sequence (as wave_half_extend); a bounded half
-    // may take it only when no earlier alignment reaches into its rows
-    if (!BOUND || bounds_none(B, b0, nacc, at, dir)) {
-        const uint32_t n = min(lenA, lenB);
-        const int32_t st = dir > 0 ? (int32_t)at : (int32_t)(at - n), sq = dir > 0 ? (int32_t)aq : (int32_t)(aq - n);
-        bool ok = true;
-        uint64_t ncg = 0;
-        for (uint32_t k0 = 0; k0 < n; k0 += 64u * 32u) {
-            uint32_t k = k0 + lane * 32u;
-            if (k < n) {
-                const Win32 tw = win32(T, st + (int32_t)k), qw = win32(Q, sq + (int32_t)k);
-                uint32_t bad = (tw.lo ^ qw.lo) | (tw.hi ^ qw.hi) | tw.nm | qw.nm;
-                uint32_t rem = n - k, mask = rem < 32 ? (1u << rem) - 1u : 0xFFFFFFFFu;
-                if (bad & mask) ok = false;
-                ncg += __popc((tw.lo ^ tw.hi) & mask);
-            }
-            if (__ballot(!ok)) break;
-        }
-        if (!__ballot(!ok)) {
-            for (int o = 32; o > 0; o >>= 1) ncg += __shfl_xor(ncg, o);
-            uint64_t sc = 100ull * ncg + 91ull * ((uint64_t)n - ncg);
-            best.score = (int32_t)(uint32_t)sc; best.maxcols = (uint32_t)(sc >> 32); best.i = n; best.j = n; best.nm = n; best.nx = 0;
-            return best;
-        }
-    }
+    // a bounded half may take the exact shortcut only when no earlier alignment reaches into its rows
+    if ((!BOUND || bounds_none(B, b0, nacc, at, dir)) && identical_suffix(T, Q, at, aq, dir, best)) return best;
     // biased score bytes of the four query bases for each target base (index lo | hi << 1)
     uint32_t tab[4];
 #pragma unroll
@@ -950,15 +704,6 @@ __global__ __launch_bounds__(64) void k6_dp1_bounded(const Group *__restrict__ g
         sweep[job.slot] = sw;
         if (r.overflow) ovf_list[atomicAdd(novf, 1u)] = blockIdx.x;
     }
-}
-
-__global__ __launch_bounds__(C4_THREADS) void k6_dp4(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
-                                                     HalfResult *__restrict__ res, int32_t O, int32_t E, int32_t Y) {
-    __shared__ C4Shared sh;
-    const DpJob job = jobs[blockIdx.x];
-    const Group &G = groups[job.group];
-    HalfResult r = block_half_extend(sh, G.T, G.Q, job.at, job.aq, job.dir, O, E, Y);
-    if (threadIdx.x == 0) res[job.slot] = r;
 }
 
 // Anchor = centre of the best 31-column window of the HSP (first maximum).  Windows are cut into
@@ -1142,24 +887,16 @@ __global__ __launch_bounds__(64) void k6_pick(Group *__restrict__ groups, const 
     }
 }
 
-__global__ __launch_bounds__(64) void k6_dp(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
-                                            HalfResult *__restrict__ res, int32_t O, int32_t E, int32_t Y,
-                                            int only_overflowed, int32_t cap) {
-    const DpJob job = jobs[blockIdx.x];
-    if (only_overflowed && !res[job.slot].overflow) return;
-    const Group &G = groups[job.group];
-    HalfResult r = wave_half_extend<16>(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, cap);
-    if (threadIdx.x == 0) res[job.slot] = r;
-}
-
-// second chance for half extensions whose band outgrew the 1024-column window: 2048 columns
+// second chance for half extensions that outgrew the lean kernel (band beyond its 896-column window, 65 535 rows): 2048
+// columns.  every: all jobs of the round, not only the overflowed ones (penalties outside the lean kernel's domain)
 __global__ __launch_bounds__(64) void k6_dp_wide(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
                                                  HalfResult *__restrict__ res, int32_t O, int32_t E, int32_t Y,
-                                                 unsigned int *__restrict__ novf, unsigned int *__restrict__ ovf_list, int32_t cap) {
+                                                 unsigned int *__restrict__ novf, unsigned int *__restrict__ ovf_list, int32_t cap,
+                                                 int every) {
     const DpJob job = jobs[blockIdx.x];
-    if (!res[job.slot].overflow) return;
+    if (!every && !res[job.slot].overflow) return;
     const Group &G = groups[job.group];
-    HalfResult r = wave_half_extend<32>(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, cap);
+    HalfResult r = wave_half_extend_2048(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, cap);
     if (threadIdx.x == 0) {
         res[job.slot] = r;
         if (r.overflow) ovf_list[atomicAdd(novf, 1u)] = blockIdx.x;  // band beyond 2048 columns: k6_dp_any
@@ -1169,7 +906,7 @@ __global__ __launch_bounds__(64) void k6_dp_wide(const Group *__restrict__ group
 // ---- last resort: a half extension whose band does not fit 2048 columns (tandem arrays: every shift by a
 // period scores almost as well, so the live band grows with the array).  One workgroup of 1024 threads, the DP
 // rows in global memory as a ring of ANY_COLS columns (two rows: previous / current), three passes per row
-// with the same rules and tie-breaks as wave_half_extend.  Slow (a few microseconds per row plus ~1 ns per
+// with the same rules and tie-breaks as wave_half_extend_2048.  Slow (a few microseconds per row plus ~1 ns per
 // live cell) but exact; only jobs that overflowed the register kernels come here.
 constexpr uint32_t ANY_COLS = 1u << 16;   // live band + one row's growth must stay below this
 constexpr int ANY_THREADS = 1024;
@@ -1866,19 +1603,13 @@ static int trace_round(Group *d_groups, uint32_t h0, const mimeo_params *p, uint
     if (!e0) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
     HIP_TRY(hipEventRecord(e0, st));
     bc.P.blk = (const PathBlock *)g_arena.p;   // the arena may just have grown
+    const auto trace = bounded ? k6_trace<true> : k6_trace<false>;
     for (size_t c = 0; c + 1 < cut.size(); c++)
-        if (cut[c + 1] > cut[c] && ++*slices) {
-            if (bounded)
-                hipLaunchKernelGGL(k6_trace<true>, dim3(cut[c + 1] - cut[c]), dim3(TR_THREADS), 0, st, (const Group *)d_groups,
-                                   (const DpJob *)g_jobs.p, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
-                                   (uint8_t *)g_pool.p, (PathBlock *)g_arena.p, (unsigned long long)(g_arena.cap / sizeof(PathBlock)),
-                                   (uint2 *)g_pidx.p, (unsigned int *)g_tctr.p, O, E, Y, bc);
-            else
-                hipLaunchKernelGGL(k6_trace<false>, dim3(cut[c + 1] - cut[c]), dim3(TR_THREADS), 0, st, (const Group *)d_groups,
-                                   (const DpJob *)g_jobs.p, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
-                                   (uint8_t *)g_pool.p, (PathBlock *)g_arena.p, (unsigned long long)(g_arena.cap / sizeof(PathBlock)),
-                                   (uint2 *)g_pidx.p, (unsigned int *)g_tctr.p, O, E, Y, bc);
-        }
+        if (cut[c + 1] > cut[c] && ++*slices)
+            hipLaunchKernelGGL(trace, dim3(cut[c + 1] - cut[c]), dim3(TR_THREADS), 0, st, (const Group *)d_groups,
+                               (const DpJob *)g_jobs.p, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
+                               (uint8_t *)g_pool.p, (PathBlock *)g_arena.p, (unsigned long long)(g_arena.cap / sizeof(PathBlock)),
+                               (uint2 *)g_pidx.p, (unsigned int *)g_tctr.p, O, E, Y, bc);
     HIP_TRY(hipEventRecord(e1, st));
     unsigned int c3[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(c3, g_tctr.p, 12, hipMemcpyDeviceToHost, st));
@@ -1898,6 +1629,77 @@ static int trace_round(Group *d_groups, uint32_t h0, const mimeo_params *p, uint
     return 0;
 }
 
+// The DP kernels of a round over its n jobs, each taking the jobs that the one before could not hold: the lean kernel, the
+// 2048-column kernel (not in bounded mode: it knows no bounds), the global-memory kernel.  The lean kernel's dead-cell
+// arithmetic needs the penalties to stay far below 2^29 / 1024; beyond that every job starts at the second kernel of its mode.
+static int dp_round(Group *d_groups, uint32_t n, const mimeo_params *p, int32_t cap, bool bounded, const BoundCtx &bc,
+                    unsigned int *novf) {
+    hipStream_t st = stream();
+    int rc;
+    const Group *groups = d_groups;
+    const DpJob *jobs = (const DpJob *)g_jobs.p;
+    HalfResult *res = (HalfResult *)g_res.p;
+    HalfSweep *sweep = bounded ? (HalfSweep *)g_sweep.p : nullptr;
+    unsigned int *list = (unsigned int *)g_ovf_list.p;
+    const int32_t O = p->gap_open, E = p->gap_extend, Y = p->ydrop;
+    const bool lean_ok = E <= (1 << 16) && O <= (1 << 24) && Y <= (1 << 28);
+    if (bounded) {
+        if (lean_ok) hipLaunchKernelGGL(k6_dp1_bounded, dim3(n), dim3(64), 0, st, groups, jobs, res, sweep, O, E, Y, bc, novf, list);
+        else hipLaunchKernelGGL(k6_list_all, dim3((n + 255) / 256), dim3(256), 0, st, n, novf, list);
+    } else {
+        if (lean_ok) hipLaunchKernelGGL(k6_dp1, dim3(n), dim3(64), 0, st, groups, jobs, res, O, E, Y);
+        hipLaunchKernelGGL(k6_dp_wide, dim3(n), dim3(64), 0, st, groups, jobs, res, O, E, Y, novf, list, cap, lean_ok ? 0 : 1);
+    }
+    // bands beyond 2048 columns (tandem arrays): the global-memory kernel, a few jobs at a time
+    unsigned int nov = 0;
+    HIP_TRY(hipMemcpyAsync(&nov, novf, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!nov) return 0;
+    const unsigned int slots = std::min<unsigned int>(nov, 32u);
+    if ((rc = g_any.reserve((size_t)slots * ANY_SLOT_WORDS * 4))) return rc;
+    const auto any = bounded ? k6_dp_any<true> : k6_dp_any<false>;
+    for (unsigned int f = 0; f < nov; f += slots)
+        hipLaunchKernelGGL(any, dim3(std::min(slots, nov - f)), dim3(ANY_THREADS), 0, st, groups, jobs, (const unsigned int *)list, f, res,
+                           (uint32_t *)g_any.p, O, E, Y, cap, bc, sweep);
+    return 0;
+}
+
+// MIMEO_K6_STATS: what the DP kernels made of the round's n jobs, on stderr; bounded mode: *bound_jobs counts those that met a bound
+static int round_stats(uint32_t n, uint64_t nhsps, bool bounded, unsigned long long *bound_jobs) {
+    std::vector<DpJob> hj(n);
+    std::vector<HalfResult> hall((size_t)nhsps * 2), hr(n);
+    HIP_TRY(hipStreamSynchronize(stream()));
+    HIP_TRY(hipMemcpy(hj.data(), g_jobs.p, (size_t)n * sizeof(DpJob), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hall.data(), g_res.p, hall.size() * sizeof(HalfResult), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < hr.size(); k++) hr[k] = hall[hj[k].slot];
+    unsigned long long hist[9] = {0}, rows = 0, maxr = 0, shortcut = 0;
+    for (auto &r : hr) {
+        if (!r.rows) { shortcut++; continue; }
+        hist[std::min<uint32_t>(8, r.maxcols / 128)]++; rows += r.rows; maxr = std::max<unsigned long long>(maxr, r.rows);
+    }
+    unsigned long long rebased = 0;
+    for (auto &r : hr) if (r.base_lo | r.base_hi) rebased++;
+    fprintf(stderr, "[k6] jobs %u shortcut %llu (rebased in k6_dp_any: %llu) rows total %llu max %llu band<128..>=1024:", n, shortcut, rebased, rows, maxr);
+    for (int b = 0; b < 9; b++) fprintf(stderr, " %llu", hist[b]);
+    fprintf(stderr, "\n");
+    {
+        unsigned long long fine[34] = {0};
+        for (auto &r : hr) if (r.rows) fine[std::min<uint32_t>(33, r.maxcols / 32)]++;
+        fprintf(stderr, "[k6] widest band, buckets of 32 columns from 448:");
+        for (int b = 14; b < 34; b++) fprintf(stderr, " %llu", fine[b]);
+        fprintf(stderr, "\n");
+    }
+    int shown = 0;
+    for (auto &r : hr)
+        if (!r.rows && shown < 8) { fprintf(stderr, "  [k6] zero-row job: score %d i %u j %u nm %u nx %u ovf %u\n", r.score, r.i, r.j, r.nm, r.nx, r.overflow); shown++; }
+    if (bounded) {
+        std::vector<HalfSweep> hs((size_t)nhsps * 2);
+        HIP_TRY(hipMemcpy(hs.data(), g_sweep.p, hs.size() * sizeof(HalfSweep), hipMemcpyDeviceToHost));
+        for (auto &j : hj) *bound_jobs += hs[j.slot].nbound ? 1u : 0u;
+    }
+    return 0;
+}
+
 int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, const uint32_t *d_order,
                   uint64_t nhsps, const mimeo_params *p, mimeo_alignment *d_aln) {
     if (!ngroups || !nhsps) return 0;
@@ -1906,9 +1708,9 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
     if (!p->gapped) {
         hipLaunchKernelGGL(k6_ungapped, dim3(ngroups), dim3(256), 0, st, d_groups, d_sorted, d_order, d_aln);
     } else {
+        // development switches: read once per call, not per round (MIMEO_K6_TRACE_POOL_MB: trace_pool_budget)
         uint32_t bmax = 8192u / ngroups;  // anchors per group and round (200 units: 32 -> one large round and a short one)
         if (getenv("MIMEO_K6_BMAX")) bmax = (uint32_t)atoi(getenv("MIMEO_K6_BMAX"));
-        const char *kmode = getenv("MIMEO_K6_KERNEL");       // development switches: read once per call, not per round
         const bool k6_stats = getenv("MIMEO_K6_STATS") != nullptr;
         // 32-bit DP cells: beyond this score a half extension goes to (or, in k6_dp_any, rebases its cells in) the last kernel;
         // MIMEO_K6_SCORE_CAP lowers it so that tests of ordinary size take that road
@@ -1947,121 +1749,30 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
             pv = PathView{(const uint2 *)g_pidx.p, nullptr, (uint32_t *)g_accrank.p};
         }
         if (bounded && (rc = g_sweep.reserve((size_t)nhsps * 2 * sizeof(HalfSweep)))) return rc;
+        const auto pick = path ? k6_pick<true> : k6_pick<false>;
+        const auto resolve = bounded ? k6_resolve<true, true> : path ? k6_resolve<true, false> : k6_resolve<false, false>;
+        const HalfSweep *sweep = bounded ? (const HalfSweep *)g_sweep.p : nullptr;
         for (;;) {
             HIP_TRY(hipMemsetAsync(g_cnt.p, 0, 16, st));
             unsigned int *njobs = (unsigned int *)g_cnt.p, *remaining = njobs + 1, *novf = njobs + 2;
             pv.blk = (const PathBlock *)g_arena.p;   // the arena may have grown in the last round
-            if (path)
-                hipLaunchKernelGGL(k6_pick<true>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                                   (const mimeo_alignment *)d_aln, bmax, (uint8_t *)g_astate.p, (uint8_t *)g_astate.p + nhsps,
-                                   (DpJob *)g_jobs.p, njobs, pv);
-            else
-                hipLaunchKernelGGL(k6_pick<false>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                                   (const mimeo_alignment *)d_aln, bmax, (uint8_t *)g_astate.p, (uint8_t *)g_astate.p + nhsps,
-                                   (DpJob *)g_jobs.p, njobs, pv);
-            unsigned int h[2] = {0, 0};
-            HIP_TRY(hipMemcpyAsync(h, g_cnt.p, 4, hipMemcpyDeviceToHost, st));
+            hipLaunchKernelGGL(pick, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p, (const mimeo_alignment *)d_aln,
+                               bmax, (uint8_t *)g_astate.p, (uint8_t *)g_astate.p + nhsps, (DpJob *)g_jobs.p, njobs, pv);
+            unsigned int h0 = 0;   // jobs of the round
+            HIP_TRY(hipMemcpyAsync(&h0, njobs, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            if (h[0]) {
-                // MIMEO_K6_KERNEL (development A/B): "dp4" = the four-wavefront kernel then wave_half_extend<16>, "dp" = the
-                // latter alone; default = the lean single-wavefront kernel (its dead-cell arithmetic needs the
-                // penalties to stay far below 2^29 / 1024)
-                const bool lean_ok = p->gap_extend <= (1 << 16) && p->gap_open <= (1 << 24) && p->ydrop <= (1 << 28);
+            if (h0) {
                 const BoundCtx bc{(const mimeo_alignment *)d_aln, (const uint2 *)g_anchors.p, pv};
-                if (bounded) {
-                    // the bounded lean kernel; what does not fit it goes straight to the bounded k6_dp_any
-                    if (lean_ok)
-                        hipLaunchKernelGGL(k6_dp1_bounded, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups, (const DpJob *)g_jobs.p,
-                                           (HalfResult *)g_res.p, (HalfSweep *)g_sweep.p, p->gap_open, p->gap_extend, p->ydrop, bc, novf,
-                                           (unsigned int *)g_ovf_list.p);
-                    else
-                        hipLaunchKernelGGL(k6_list_all, dim3((h[0] + 255) / 256), dim3(256), 0, st, h[0], novf, (unsigned int *)g_ovf_list.p);
-                } else if (lean_ok && !kmode) {
-                    hipLaunchKernelGGL(k6_dp1, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups, (const DpJob *)g_jobs.p,
-                                       (HalfResult *)g_res.p, p->gap_open, p->gap_extend, p->ydrop);
-                } else {
-                    const bool use4 = !kmode || !strcmp(kmode, "dp4");
-                    if (use4)
-                        hipLaunchKernelGGL(k6_dp4, dim3(h[0]), dim3(C4_THREADS), 0, st, (const Group *)d_groups,
-                                           (const DpJob *)g_jobs.p, (HalfResult *)g_res.p, p->gap_open, p->gap_extend, p->ydrop);
-                    hipLaunchKernelGGL(k6_dp, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups, (const DpJob *)g_jobs.p,
-                                       (HalfResult *)g_res.p, p->gap_open, p->gap_extend, p->ydrop, use4 ? 1 : 0, cap);
-                }
-                if (!bounded)
-                    hipLaunchKernelGGL(k6_dp_wide, dim3(h[0]), dim3(64), 0, st, (const Group *)d_groups,
-                                       (const DpJob *)g_jobs.p, (HalfResult *)g_res.p, p->gap_open, p->gap_extend, p->ydrop, novf,
-                                       (unsigned int *)g_ovf_list.p, cap);
-                // bands beyond 2048 columns (tandem arrays): the global-memory kernel, a few jobs at a time
-                unsigned int nov = 0;
-                HIP_TRY(hipMemcpyAsync(&nov, novf, 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (nov) {
-                    const unsigned int slots = std::min<unsigned int>(nov, 32u);
-                    if ((rc = g_any.reserve((size_t)slots * ANY_SLOT_WORDS * 4))) return rc;
-                    for (unsigned int f = 0; f < nov; f += slots) {
-                        if (bounded)
-                            hipLaunchKernelGGL(k6_dp_any<true>, dim3(std::min(slots, nov - f)), dim3(ANY_THREADS), 0, st, (const Group *)d_groups,
-                                               (const DpJob *)g_jobs.p, (const unsigned int *)g_ovf_list.p, f, (HalfResult *)g_res.p,
-                                               (uint32_t *)g_any.p, p->gap_open, p->gap_extend, p->ydrop, cap, bc, (HalfSweep *)g_sweep.p);
-                        else
-                            hipLaunchKernelGGL(k6_dp_any<false>, dim3(std::min(slots, nov - f)), dim3(ANY_THREADS), 0, st, (const Group *)d_groups,
-                                               (const DpJob *)g_jobs.p, (const unsigned int *)g_ovf_list.p, f, (HalfResult *)g_res.p,
-                                               (uint32_t *)g_any.p, p->gap_open, p->gap_extend, p->ydrop, cap, bc, (HalfSweep *)nullptr);
-                    }
+                if ((rc = dp_round(d_groups, h0, p, cap, bounded, bc, novf))) return rc;
+                if (k6_stats && (rc = round_stats(h0, nhsps, bounded, &bound_jobs))) return rc;
+                if (path) {
+                    rounds++;
+                    if ((rc = trace_round(d_groups, h0, p, pool_budget, &arena_used, &ms_trace, &trace_slices, &largest, bounded, bc))) return rc;
+                    pv.blk = (const PathBlock *)g_arena.p;
                 }
             }
-            if (k6_stats && h[0]) {
-                std::vector<DpJob> hj(h[0]);
-                std::vector<HalfResult> hall((size_t)nhsps * 2), hr(h[0]);
-                HIP_TRY(hipStreamSynchronize(st));
-                HIP_TRY(hipMemcpy(hj.data(), g_jobs.p, (size_t)h[0] * sizeof(DpJob), hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(hall.data(), g_res.p, hall.size() * sizeof(HalfResult), hipMemcpyDeviceToHost));
-                for (size_t k = 0; k < hr.size(); k++) hr[k] = hall[hj[k].slot];
-                unsigned long long hist[9] = {0}, rows = 0, maxr = 0, shortcut = 0;
-                for (auto &r : hr) {
-                    if (!r.rows) { shortcut++; continue; }
-                    hist[std::min<uint32_t>(8, r.maxcols / 128)]++; rows += r.rows; maxr = std::max<unsigned long long>(maxr, r.rows);
-                }
-                unsigned long long rebased = 0;
-                for (auto &r : hr) if (r.base_lo | r.base_hi) rebased++;
-                fprintf(stderr, "[k6] jobs %u shortcut %llu (rebased in k6_dp_any: %llu) rows total %llu max %llu band<128..>=1024:", h[0], shortcut, rebased, rows, maxr);
-                for (int b = 0; b < 9; b++) fprintf(stderr, " %llu", hist[b]);
-                fprintf(stderr, "\n");
-                {
-                    unsigned long long fine[34] = {0};
-                    for (auto &r : hr) if (r.rows) fine[std::min<uint32_t>(33, r.maxcols / 32)]++;
-                    fprintf(stderr, "[k6] widest band, buckets of 32 columns from 448:");
-                    for (int b = 14; b < 34; b++) fprintf(stderr, " %llu", fine[b]);
-                    fprintf(stderr, "\n");
-                }
-                int shown = 0;
-                for (auto &r : hr)
-                    if (!r.rows && shown < 8) { fprintf(stderr, "  [k6] zero-row job: score %d i %u j %u nm %u nx %u ovf %u\n", r.score, r.i, r.j, r.nm, r.nx, r.overflow); shown++; }
-            }
-            if (bounded && k6_stats && h[0]) {   // jobs of the round that met a bound
-                std::vector<DpJob> hj(h[0]);
-                std::vector<HalfSweep> hs((size_t)nhsps * 2);
-                HIP_TRY(hipStreamSynchronize(st));
-                HIP_TRY(hipMemcpy(hj.data(), g_jobs.p, (size_t)h[0] * sizeof(DpJob), hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(hs.data(), g_sweep.p, hs.size() * sizeof(HalfSweep), hipMemcpyDeviceToHost));
-                for (auto &j : hj) bound_jobs += hs[j.slot].nbound ? 1u : 0u;
-            }
-            if (path && h[0]) {
-                rounds++;
-                if ((rc = trace_round(d_groups, h[0], p, pool_budget, &arena_used, &ms_trace, &trace_slices, &largest, bounded,
-                                      BoundCtx{(const mimeo_alignment *)d_aln, (const uint2 *)g_anchors.p, pv})))
-                    return rc;
-                pv.blk = (const PathBlock *)g_arena.p;
-            }
-            if (bounded)
-                hipLaunchKernelGGL((k6_resolve<true, true>), dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv, (const HalfSweep *)g_sweep.p);
-            else if (path)
-                hipLaunchKernelGGL(k6_resolve<true>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv, (const HalfSweep *)nullptr);
-            else
-                hipLaunchKernelGGL(k6_resolve<false>, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p,
-                                   (const HalfResult *)g_res.p, d_aln, (uint8_t *)g_astate.p, remaining, pv, (const HalfSweep *)nullptr);
+            hipLaunchKernelGGL(resolve, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_anchors.p, (const HalfResult *)g_res.p,
+                               d_aln, (uint8_t *)g_astate.p, remaining, pv, sweep);
             unsigned int h4[4] = {0, 0, 0, 0};
             HIP_TRY(hipMemcpyAsync(h4, g_cnt.p, 16, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));

@@ -106,8 +106,8 @@ def test_align_with_n_and_lowercase(eng):
 
 
 def test_wide_bands_all_kernels(eng):
-    """A large y-drop widens the DP band past the 1024-column register window (the 2048-column kernel takes over)
-    and then past 2048 columns (the global-memory kernel takes over): identical results each time."""
+    """A large y-drop widens the DP band past the lean kernel's 896-column register window (the 2048-column kernel takes
+    over) and then past 2048 columns (the global-memory kernel takes over): identical results each time."""
     from oracle import oracle as O
     names, seqs = synth_genome(97, 120_000, 2, repeat_frac=0.2, families=2, cons_len=(800, 2000), max_div=0.1)
     g = eng.Genome(names, seqs)
@@ -116,6 +116,25 @@ def test_wide_bands_all_kernels(eng):
         exp = O.align_pair(seqs[0].tobytes(), seqs[1].tobytes(), O.default_params(ydrop=yd))
         assert exp.size > 2
         _cmp(got, exp, ('wide', yd), ordered=True)
+    g.close()
+
+
+# penalties outside the lean kernel's domain (gap extend <= 2^16, gap open <= 2^24, y-drop <= 2^28), one at a time
+BEYOND_LEAN = [{'gap_extend': 70000}, {'gap_open': (1 << 24) + 1}, {'ydrop': (1 << 28) + 1}]
+
+
+@pytest.mark.parametrize('kw', BEYOND_LEAN, ids=lambda kw: next(iter(kw)))
+def test_penalties_beyond_the_lean_kernel(eng, kw):
+    """Unbounded runs whose penalties the lean kernel cannot hold: every job of a round goes to the 2048-column kernel.
+    The two large gap penalties keep the band narrow; under the huge y-drop every column stays alive, so a half with
+    more than 2016 query columns left overflows that kernel too and k6_dp_any finishes it."""
+    from oracle import oracle as O
+    names, seqs = synth_genome(97, 6000, 2, repeat_frac=0.3, families=2, cons_len=(800, 1500), max_div=0.1)
+    g = eng.Genome(names, seqs)
+    got = eng.align_pair(g, 0, g, 1, eng.default_params(**kw))
+    exp = O.align_pair(seqs[0].tobytes(), seqs[1].tobytes(), O.default_params(**kw))
+    assert exp.size >= 1
+    _cmp(got, exp, kw, ordered=True)
     g.close()
 
 
@@ -148,8 +167,8 @@ def test_tandem_arrays_default_parameters(eng):
 @pytest.mark.parametrize('cap', [None, '100000'])
 def test_long_extension_beyond_packed_counts(eng, monkeypatch, cap):
     """A 300 kb alignment with 3 % substitutions and a few indels: each half extension runs for more than
-    65535 rows, past what the packed match/mismatch counters of the four-wavefront DP kernel hold, so the
-    single-wavefront kernel must take over — same alignment, same identity counts as the oracle.
+    65535 rows, past what the packed 16-bit counts of the lean kernel (896 columns) hold, so the 2048-column
+    kernel with its unpacked counts must take over — same alignment, same identity counts as the oracle.
 
     cap = 100000: the score beyond which the 2048-column kernel hands a half extension to k6_dp_any, and beyond which that
     kernel moves its 32-bit cells down (2 * 10^9 in production: 20 Mbp of near-identity in one alignment; the oracle

@@ -167,7 +167,7 @@ def test_long_half_under_a_low_score_cap(eng, monkeypatch):
     monkeypatch.delenv('MIMEO_K6_SCORE_CAP')
 
 
-def test_the_three_argument_errors(eng, monkeypatch):
+def test_the_two_argument_errors(eng):
     import ctypes as C
     from mimeo_amd import _ffi
     _, seqs = flanked_tandem_genome(1, 1, flank=2000)
@@ -179,9 +179,6 @@ def test_the_three_argument_errors(eng, monkeypatch):
 
     assert rc_of(eng.default_params(anchor_rule=1, bound_extensions=2)) == -1 and 'bound_extensions' in eng.last_error()   # MIMEO_ERR_ARG
     assert rc_of(eng.default_params(anchor_rule=0, bound_extensions=1)) == -1 and 'bound_extensions' in eng.last_error()
-    monkeypatch.setenv('MIMEO_K6_KERNEL', 'dp4')
-    assert rc_of(eng.default_params(anchor_rule=1, bound_extensions=1)) == -1 and 'MIMEO_K6_KERNEL' in eng.last_error()
-    monkeypatch.delenv('MIMEO_K6_KERNEL')
     assert rc_of(eng.default_params(anchor_rule=1, bound_extensions=1)) == 0
     if ptr.value:
         _ffi.load().mimeo_free(ptr)

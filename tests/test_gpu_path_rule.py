@@ -106,7 +106,7 @@ def test_path_rule_all_layouts(eng, monkeypatch, capfd):
     monkeypatch.delenv('MIMEO_K6_STATS')
     pool_mb = str(int(float(line.split('largest half ')[1].split()[0])) + 1)
     for env in ({'MIMEO_PACK': '0'}, {'MIMEO_MIRROR': '0'}, {'MIMEO_PACK': '0', 'MIMEO_INDEX_BUDGET_MB': '300'},
-                {'MIMEO_K6_BMAX': '1'}, {'MIMEO_K6_BMAX': '4'}, {'MIMEO_K6_KERNEL': 'dp4'}, {'MIMEO_K6_KERNEL': 'dp'},
+                {'MIMEO_K6_BMAX': '1'}, {'MIMEO_K6_BMAX': '4'},
                 {'MIMEO_K6_TRACE_POOL_MB': pool_mb, 'MIMEO_K6_STATS': '1'}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -160,6 +160,21 @@ def test_path_rule_wide_bands_long_halves_and_self(eng, monkeypatch):
     g = eng.Genome(tn, tseqs)
     for k in (0, 1):
         _cmp(eng.align_pair(g, k, g, k, eng.default_params(anchor_rule=1)), exp[3 + k], ('self', k))
+    g.close()
+
+
+def test_path_rule_penalties_beyond_the_lean_kernel(eng):
+    """Penalties the lean kernel cannot hold (every job of a round goes to the 2048-column kernel): the traceback re-runs
+    those halves and the alignments equal the oracle's.  The third set of test_gpu_align's BEYOND_LEAN, a y-drop beyond
+    2^28, is left to the box rule there: the traceback sizes a row by y-drop / gap extend, 18 million columns, and would
+    reserve gigabytes of trace pool for a 925 bp alignment."""
+    names, seqs = synth_genome(97, 6000, 2, repeat_frac=0.3, families=2, cons_len=(800, 1500), max_div=0.1)
+    sets = [{'gap_extend': 70000}, {'gap_open': (1 << 24) + 1}]
+    exp = oracle_many([(seqs[0].tobytes(), seqs[1].tobytes(), 1, kw) for kw in sets])
+    g = eng.Genome(names, seqs)
+    for kw, e in zip(sets, exp):
+        assert e.size >= 1
+        _cmp(eng.align_pair(g, 0, g, 1, eng.default_params(anchor_rule=1, **kw)), e, kw)
     g.close()
 
 
