@@ -190,10 +190,11 @@ struct ExtStats {
     uint64_t scan_bytes_algorithmic = 0, scan_bytes_kernel = 0, heavy_launches = 0, heavy_kernel_launches = 0;
     float ms_heavy = 0, ms_k34 = 0, ms_walk = 0, ms_tails = 0;  // ms_k34: the K34 launches alone (event pair per launch)  // ms_walk: the exact walks of the walk queue (part of ms_tails)
 };
-// The extension stage of one batch: heavy kernel per unit (K34 fused seed scan + pre-filter + exact walks; or, for
-// A/B checks, the stand-alone K3 join + K4 fast kernel of round 1) appending to batch-wide queues, then the tails ONCE
-// per batch: walks beyond the frame, k4_diag0 of the self units, ONE radix sort of the followers of all units,
-// segment resolution, entropy.  Two host synchronisations per batch.  Leaves nhsp HSPs in hsps / hsp_unit (device).
+// The extension stage of one batch: the heavy phase (K34 fused seed scan + pre-filter over all units of the batch in one
+// launch, the exact walks of the hits it passes on; or, MIMEO_HEAVY=v1 for A/B checks, the stand-alone K3 join + K4 fast
+// kernel of round 1 per unit) appending to batch-wide queues, then the tails ONCE per batch: walks beyond the frame,
+// k4_diag0 of the self units, ONE radix sort of the followers of all units, segment resolution, entropy.  Two host
+// synchronisations per batch.  Leaves nhsp HSPs in hsps / hsp_unit (device).
 struct ExtBatch {
     DeviceBuf units, ctr, cand, fkey, fkey2, fprev, fprev2, medq, medu, longq, longu, walkq, flags, segs, tmp, nsel, bigseg, hsps,
         hsp_unit, unit_hits, tile_hits, selfs, hits, bigcand, bigacc, heavy;
@@ -210,9 +211,9 @@ struct ExtBatch {
     // the queues of every later call on any other (a tandem-array job of 1e6 expected hits left boosts of ~100-300; the C4
     // row after it was cut into 125 batches instead of one, and a C2 call after that asked for 190 GiB of queues)
     void new_call() { boost_f = boost_m = boost_l = boost_c = boost_w = 1.0; }
-    // run = start (the heavy phase of the batch is enqueued on the calling thread's stream, nothing is waited for) + finish
-    // (tails on the calling thread's stream at that time, which may be another one: two host round trips; a batch whose queues
-    // overflowed is repeated there with room).  The pipeline starts the next batch before it finishes this one.
+    // run = start (sizes the queues, enqueues the heavy phase on the calling thread's stream, waits for nothing) + finish (the
+    // tails on the same stream: two host round trips; a batch whose queues overflowed is repeated there with room).  The
+    // pipeline only calls run, one batch at a time: a batch is finished before the next one starts.
     // mirror_dst (optional, one entry per unit): unit u's HSPs are also emitted transposed (target <-> query) for unit
     // mirror_dst[u] (NO_MIRROR: none).  The plus-strand units (A, B) and (B, A) of a self job have transposed HSP sets —
     // seeds, x-drop walks, the per-diagonal rule, entropy and HOXD70 are all symmetric — so one heavy phase serves both

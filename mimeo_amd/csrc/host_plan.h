@@ -1,9 +1,11 @@
 // host_plan.h — HIP-free planning logic of the pipeline: which scaffolds are concatenated into which super-scaffold
-// (pack.hip) and whether a pair list is a full cross product (pipeline.hip, run_packed).  Kept apart from the device
-// code so that it runs under the CPU sanitizers (tests/sanitize/host_sanitize.cc, tests/test_host_sanitize.py).
+// (pack.hip), whether a pair list is a full cross product, which pairs share a plus strand, and how the units of a call
+// are cut into index blocks and batches (pipeline.hip).  Kept apart from the device code so that it runs under the CPU
+// sanitizers (tests/sanitize/host_sanitize.cc, tests/test_host_sanitize.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <map>
 #include <utility>
 #include <vector>
 
@@ -62,6 +64,80 @@ inline CrossProduct cross_product(const uint32_t *pair_t, const uint32_t *pair_q
     }
     c.full = c.distinct == c.pairidx.size();
     return c;
+}
+
+// Seed hits a unit of nt x nq indexed positions yields on random sequence (13 words within one transition of each of 2^24
+// keys): what batches are cut by and queues are sized from.
+inline double expected_seed_hits(uint64_t nt, uint64_t nq) {
+    const double t = (double)nt, q = (double)nq;
+    return 13.0 * t * q / 16777216.0;
+}
+
+// Index blocks.  units: anything with a target key .t and a query key .q; t_bytes / q_bytes: index bytes a key still costs
+// (indexed by key; 0: already there).  When the indexes of all keys named exceed the budget the keys are ranked and the unit
+// matrix is cut into blocks of Bt target ranks x Bq query ranks whose indexes fit, half the budget to each side: the units
+// are reordered block by block, target-major inside a block and stable otherwise (the two strands of a pair stay adjacent).
+// Returns the unit index where each block ends; one block, the order unchanged, when everything fits.
+template <typename Unit>
+inline std::vector<size_t> index_blocks(std::vector<Unit> &units, const std::vector<uint64_t> &t_bytes, const std::vector<uint64_t> &q_bytes,
+                                        uint64_t budget) {
+    std::map<uint32_t, uint64_t> tblk, qblk;   // key -> rank, then block
+    for (const Unit &u : units) { tblk[u.t]; qblk[u.q]; }
+    uint64_t need = 0, tmax = 1, qmax = 1;
+    for (auto &kv : tblk) { need += t_bytes[kv.first]; tmax = std::max(tmax, t_bytes[kv.first]); }
+    for (auto &kv : qblk) { need += q_bytes[kv.first]; qmax = std::max(qmax, q_bytes[kv.first]); }
+    if (need <= budget || units.empty()) return std::vector<size_t>{units.size()};
+    const uint64_t Bt = std::max<uint64_t>(1, budget / 2 / tmax), Bq = std::max<uint64_t>(1, budget / 2 / qmax);
+    uint64_t rt = 0, rq = 0;
+    for (auto &kv : tblk) kv.second = rt++ / Bt;
+    for (auto &kv : qblk) kv.second = rq++ / Bq;
+    auto block_of = [&](const Unit &u) { return std::make_pair(tblk[u.t], qblk[u.q]); };
+    std::stable_sort(units.begin(), units.end(), [&](const Unit &a, const Unit &b) {
+        return block_of(a) != block_of(b) ? block_of(a) < block_of(b) : a.t < b.t;
+    });
+    std::vector<size_t> block_end;
+    for (size_t i = 1; i <= units.size(); i++)
+        if (i == units.size() || block_of(units[i]) != block_of(units[i - 1])) block_end.push_back(i);
+    return block_end;
+}
+
+// Shared plus strand of a self job.  When the list names (t, q) and (q, t), t != q, both on the plus strand (strands[k] & 1),
+// and neither scaffold has a target-only seed plane (soft-masked bases), the first occurrence of (min, max) also serves
+// the first occurrence of (max, min): mirror_of[lo] = hi, served[hi] = 1.  Later occurrences are units of their own.
+constexpr uint64_t NO_PAIR = ~0ull;
+struct MirrorPairs { std::vector<uint64_t> mirror_of; std::vector<char> served; };
+inline MirrorPairs mirror_pairs(const uint32_t *pair_t, const uint32_t *pair_q, const std::vector<uint8_t> &strands,
+                                const std::vector<char> &target_plane) {
+    const uint64_t n = strands.size();
+    MirrorPairs m{std::vector<uint64_t>(n, NO_PAIR), std::vector<char>(n, 0)};
+    std::map<std::pair<uint32_t, uint32_t>, std::pair<uint64_t, uint64_t>> first;   // (min, max) -> first (min, max), first (max, min)
+    for (uint64_t k = 0; k < n; k++) {
+        const uint32_t t = pair_t[k], q = pair_q[k];
+        if (t == q || !(strands[k] & 1) || target_plane[t] || target_plane[q]) continue;
+        auto &f = first.emplace(std::make_pair(std::min(t, q), std::max(t, q)), std::make_pair(NO_PAIR, NO_PAIR)).first->second;
+        uint64_t &slot = t < q ? f.first : f.second;
+        if (slot == NO_PAIR) slot = k;
+    }
+    for (auto &kv : first)
+        if (kv.second.first != NO_PAIR && kv.second.second != NO_PAIR) { m.mirror_of[kv.second.first] = kv.second.second; m.served[kv.second.second] = 1; }
+    return m;
+}
+
+// Batch cut.  A unit takes one work slot, or two with its mirror rider (which never leaves it); the batch that starts at
+// unit b0 takes units greedily while the slots, the expected seed hits and the group weights stay within the limits — the
+// first unit whatever it costs.
+struct BatchUnit { uint32_t slots; double hits; uint64_t weight; };
+struct BatchLimits { size_t max_units; double max_hits; uint64_t max_weight; };
+struct Batch { size_t end, slots; double hits; };   // [b0, end): work slots and expected seed hits of the batch
+inline Batch batch_cut(const std::vector<BatchUnit> &units, size_t b0, size_t block_end, const BatchLimits &lim) {
+    Batch b{b0, 0, 0.0};
+    uint64_t weight = 0;
+    for (; b.end < block_end; b.end++) {
+        const BatchUnit &u = units[b.end];
+        if (b.slots && (b.slots + u.slots > lim.max_units || b.hits + u.hits > lim.max_hits || weight + u.weight > lim.max_weight)) break;
+        b.slots += u.slots; b.hits += u.hits; weight += u.weight;
+    }
+    return b;
 }
 
 }  // namespace host_plan

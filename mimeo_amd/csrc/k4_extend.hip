@@ -854,7 +854,7 @@ int ExtBatch::start(const std::vector<UnitWork> &work, const mimeo_params *p, co
     w_ = work;
     p_ = *p;
     uint64_t max_t = 0, max_q = 0;
-    double expect_hits = 0, max_unit_hits = 0;
+    double expect_hits = 0;
     std::vector<UnitDesc> &h_units = h_units_;   // a member: the copy below is asynchronous
     h_units.resize(nunits);
     h_selfs_.clear();
@@ -864,8 +864,7 @@ int ExtBatch::start(const std::vector<UnitWork> &work, const mimeo_params *p, co
         h_units[u] = w.d;
         max_t = std::max<uint64_t>(max_t, w.d.T.len);
         max_q = std::max<uint64_t>(max_q, w.d.Q.len);
-        expect_hits += 13.0 * (double)w.ti.n * (double)w.qi.n / 16777216.0;
-        max_unit_hits = std::max(max_unit_hits, 13.0 * (double)w.ti.n * (double)w.qi.n / 16777216.0);
+        expect_hits += host_plan::expected_seed_hits(w.ti.n, w.qi.n);
         if (w.d.same) h_selfs_.push_back(u);
     }
     expect_hits_ = expect_hits;
@@ -919,13 +918,12 @@ int ExtBatch::start(const std::vector<UnitWork> &work, const mimeo_params *p, co
     cap_c_ = (uint64_t)(expect_hits * 0.002 * boost_c / shrink) + (uint64_t)(1048576 / shrink) + 64;
     // the walk queue: a region of eight shards per unit, sized from the unit's expected hits (K34 passes ~4 % of the hits of
     // random sequence on)
-    (void)max_unit_hits;
     walk_entries_ = 0;
     walk_cap_u_.assign(nunits, 0);
     for (uint32_t u = 0; u < nunits; u++) {
         const UnitWork &w = work[u];
         if (!w.ti.n || !w.qi.n) continue;
-        const double e = 13.0 * (double)w.ti.n * (double)w.qi.n / 16777216.0;
+        const double e = host_plan::expected_seed_hits(w.ti.n, w.qi.n);
         walk_cap_u_[u] = (uint64_t)(e * 0.08 / 8 * 1.5 * boost_w / shrink) + (uint64_t)(16384 / shrink) + 64;
         walk_entries_ += 8 * walk_cap_u_[u];
     }

@@ -66,6 +66,33 @@ def test_soft_masked_scaffold_falls_back_to_two_scans(eng):
     g.close()
 
 
+def test_duplicate_pairs_beside_a_shared_plus_strand_on_the_unit_per_pair_path(eng, monkeypatch):
+    """A pair list that is no cross product (so: one unit per pair, no switch set) naming (0, 1) and (1, 0) twice each.  Only the
+    first occurrences share their plus strand; the later ones are units of their own.  Every occurrence returns the same
+    records — the oracle's for that pair — and the rows come in the order of the list.  Ten work slots (five pairs on two
+    strands), nine of them scanned: the plus strand of the first (1, 0) rides on the first (0, 1)."""
+    from oracle import oracle as O
+    names, seqs = synth_genome(94, 120_000, 3, repeat_frac=0.15, families=5, cons_len=(200, 2000), max_div=0.12)
+    g = eng.Genome(names, seqs)
+    for k in ('MIMEO_MIRROR', 'MIMEO_PACK'):
+        monkeypatch.delenv(k, raising=False)
+    pairs = [(0, 1), (1, 0), (0, 1), (2, 2), (1, 0)]
+    got = eng.align_pairs(g, None, pairs)
+    st = eng.stats()
+    assert st['super_units'] == 0 and st['pair_strands'] == 10 and st['scan_launches'] == 9, st
+    exp = {tq: np.sort(_oracle_pair(O, seqs[tq[0]], seqs[tq[1]])[ACOLS], order=ACOLS) for tq in set(pairs)}
+    assert all(e.size > 0 and set(e['qstrand'].tolist()) == {0, 1} for e in exp.values())   # both strands of every pair are tested
+    lo = 0
+    for t, q in pairs:   # a pair's rows are contiguous, the pairs in the order of the list
+        rows = got[lo:lo + exp[(t, q)].size]
+        lo += rows.size
+        assert (rows['tid'] == t).all() and (rows['qid'] == q).all(), (t, q)
+        a = np.sort(rows[ACOLS], order=ACOLS)
+        assert a.size == exp[(t, q)].size and (a == exp[(t, q)]).all(), (t, q)
+    assert lo == got.size
+    g.close()
+
+
 def test_units_api_rows_cover_the_job_and_give_the_same_records(eng, monkeypatch):
     """dist.units_of_row: the rows of a self job name every unit exactly once; aligned row by row through
     mimeo_align_units (plus-strand pairs in both orders in the row that owns them) the records are those of one
