@@ -328,7 +328,8 @@ int mimeo_coverage_bedgraph(const mimeo_interval *iv, uint64_t n, const uint32_t
  * scorer v2") marks; the host keeps a hit if 100*masked/len < maxtandem (wrappers.py:237-240).
  * match / mismatch / delta / minscore / maxperiod are TRF's weights and thresholds of the same
  * names (delta = indel penalty; delta <= 0: gap-free comparison); TRF's detection statistics PM and
- * PI have no counterpart.  `masked` is a caller-owned array of n entries.  maxperiod <= 64.
+ * PI have no counterpart.  `masked` is a caller-owned array of n entries.  maxperiod: 1 .. 2000
+ * (TRF's own range for the argument; parity with TRF itself unpinned), MIMEO_ERR_LIMIT outside it.
  */
 int mimeo_tandem_masked(const mimeo_genome *A, const mimeo_interval *iv, uint64_t n, int32_t match,
                         int32_t mismatch, int32_t delta, int32_t minscore, int32_t maxperiod, uint32_t *masked);

@@ -52,6 +52,16 @@ def check_common(parser, args):
     return args
 
 
+TMAXPERIOD_MAX = 2000   # TRF's own upper end for its maxperiod argument; the tandem scorer (K8) takes 1 .. 2000
+
+
+def check_tmaxperiod(parser, args):
+    """--tmaxperiod of `mimeo map` and `mimeo filter` (parser.error exits with status 2, before the engine starts)"""
+    if not 1 <= args.tmaxperiod <= TMAXPERIOD_MAX:
+        parser.error('--tmaxperiod must be in 1..%d' % TMAXPERIOD_MAX)
+    return args
+
+
 def init_logging(level):
     logging.basicConfig(level=getattr(logging, level), format='%(asctime)s %(levelname)s %(message)s', stream=sys.stderr)
 

@@ -140,5 +140,30 @@ inline Batch batch_cut(const std::vector<BatchUnit> &units, size_t b0, size_t bl
     return b;
 }
 
+// Tandem scorer beyond 64 periods (k8_tandem.hip): one wavefront works through one job = (slice, period block); block k
+// holds the periods 64k + 1 .. 64k + 64, lane = period.  A period p walks the diagonals p - b .. p + b (b = 0 for p = 1,
+// 1 for p < 5, else 2; delta <= 0: b = 0) of a slice longer than p - b, so a block has work on a slice of L bases only
+// when its smallest diagonal lies below L: the others are left out (a 300-base hit at maxperiod 2000 costs 5 waves, not
+// 32).  A wave is serial over its slice, so the longest slices come first (stable: equal lengths keep the caller's
+// order, blocks ascending inside a slice).  The device sees the list TANDEM_CHUNK_JOBS jobs at a time.
+constexpr int TANDEM_MAXPERIOD = 2000;    // TRF's own upper end for this argument
+constexpr uint32_t TANDEM_BLOCK = 64;     // periods per job
+struct TandemJob { uint32_t slice, block; };
+constexpr uint64_t TANDEM_CHUNK_BYTES = 64ull << 20;   // device bytes the job list may take
+constexpr uint64_t TANDEM_CHUNK_JOBS = TANDEM_CHUNK_BYTES / sizeof(TandemJob);
+constexpr uint32_t tandem_block_first_diagonal(uint32_t block, int delta) {   // constexpr: the kernel calls it too
+    return block == 0 ? 1u : block * TANDEM_BLOCK + 1u - (delta > 0 ? 2u : 0u);
+}
+inline std::vector<TandemJob> tandem_jobs(const std::vector<uint32_t> &lengths, int maxperiod, int delta) {
+    const uint32_t nblocks = maxperiod > 0 ? ((uint32_t)maxperiod + TANDEM_BLOCK - 1) / TANDEM_BLOCK : 0;
+    std::vector<uint32_t> order(lengths.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lengths[a] > lengths[b]; });
+    std::vector<TandemJob> jobs;
+    for (uint32_t s : order)
+        for (uint32_t k = 0; k < nblocks && tandem_block_first_diagonal(k, delta) < lengths[s]; k++) jobs.push_back(TandemJob{s, k});
+    return jobs;
+}
+
 }  // namespace host_plan
 }  // namespace mimeo

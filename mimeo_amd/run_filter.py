@@ -28,12 +28,12 @@ def mainArgs(argv=None):
     parser.add_argument('--tPM', type=int, default=80, help='Accepted for compatibility (no detection statistics: every period is tried).')
     parser.add_argument('--tPI', type=int, default=10, help='Accepted for compatibility.')
     parser.add_argument('--tminscore', type=int, default=50, help='Minimum tandem score to mask')
-    parser.add_argument('--tmaxperiod', type=int, default=50, help='Maximum period size to score (<= 64).')
+    parser.add_argument('--tmaxperiod', type=int, default=50, help='Maximum period size to score (<= 2000, TRF\'s own range). The scorer is a specification of its own: parity with TRF unpinned.')
     parser.add_argument('--maxtandem', type=float, default=40,
                         help='Max percentage of a sequence which may be masked. If exceeded, element will be discarded.')
     parser.add_argument('--loglevel', type=str, default='INFO', choices=['DEBUG', 'INFO', 'WARNING', 'ERROR', 'CRITICAL'])
     parser.add_argument('--device', type=int, default=None, help='GPU index (default 0).')
-    return parser.parse_args(argv)
+    return _cli.check_tmaxperiod(parser, parser.parse_args(argv))
 
 
 def filter_fasta(infile, outfile, tmatch=2, tmismatch=7, tminscore=50, tmaxperiod=50, maxtandem=40, verbose=False, tdelta=7):

@@ -16,12 +16,12 @@ def mainArgs(argv=None):
     for name, default, what in (('tmatch', 2, 'matching weight'), ('tmismatch', 7, 'mismatching penalty'), ('tdelta', 7, 'indel penalty'),
                                 ('tPM', 80, 'match probability: accepted for compatibility, the on-GPU scorer tries every period (no detection statistics)'),
                                 ('tPI', 10, 'indel probability: accepted for compatibility (as --tPM)'),
-                                ('tminscore', 50, 'minimum alignment score of a tandem repeat'), ('tmaxperiod', 50, 'maximum period size (<= 64)')):
+                                ('tminscore', 50, 'minimum alignment score of a tandem repeat'), ('tmaxperiod', 50, 'maximum period size (<= 2000, TRF\'s own range); the scorer is a specification of its own, parity with TRF unpinned')):
         parser.add_argument('--' + name, type=int, default=default, help='Tandem scorer (TRF parameter of the same name): %s.' % what)
     parser.add_argument('--maxtandem', type=float, default=None,
                         help='Max percentage of an A-genome alignment which may be masked by TRF.')
     parser.add_argument('--writeTRF', action='store_true', default=False, help='Write TRF-filtered alignment file.')
-    return _cli.check_common(parser, parser.parse_args(argv))
+    return _cli.check_tmaxperiod(parser, _cli.check_common(parser, parser.parse_args(argv)))
 
 
 def main(argv=None):
