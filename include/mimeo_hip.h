@@ -293,6 +293,39 @@ int mimeo_align_units(const mimeo_genome *A, const mimeo_genome *B, const uint32
                       const mimeo_params *p, mimeo_alignment **out, uint64_t *nout);
 
 /*
+ * mimeo_align_units with the alignments themselves: where the gaps are, and which base is paired with which.  `out` / `nout`
+ * are byte for byte what mimeo_align_units returns for the same arguments.  The path of alignment i is the gap-free blocks
+ * blocks[path_first[i] .. path_first[i + 1]): path_first has *nout + 1 entries, *nblocks = path_first[*nout].  All three
+ * arrays are released with mimeo_free.  Under the box rule the paths cost one more traceback of the returned alignments;
+ * a call of mimeo_align_units pays nothing for them.
+ *
+ * Coordinates of a block: `t` on the target plus strand; `q` on the strand that was aligned — for qstrand == 1 these are
+ * reverse-complement coordinates, as mimeo_seed_hit.qpos (the record's qstart / qend stay on the plus strand: with Lq the
+ * query's length, qstart = Lq - (q_last + len_last) and qend = Lq - q_first); `len` columns of the diagonal from (t, q),
+ * each a match or a mismatch.
+ *
+ * What a caller may rely on:
+ *   - the blocks of one alignment are strictly increasing in t and in q and never touch on a diagonal (two that would are
+ *     one block);
+ *   - between two consecutive blocks exactly one of t and q jumps (a gap), or both do (an insertion next to a deletion);
+ *   - the first block starts at (tstart, q_first) and the last one ends at tend;
+ *   - the sum of len over an alignment's blocks is its id_d.
+ * --gapped off: one block per alignment.  A pair with a half extension whose traceback alone exceeds the trace pool (a share
+ * of the free device memory) is left out with MIMEO_ERR_LIMIT like a pair whose band exceeds the DP limit
+ * (mimeo_get_failed_pairs) — only here, where paths are asked for.
+ *
+ * A new symbol beside the old ones: no struct changed size or meaning and no existing entry point changed, so
+ * MIMEO_ABI_VERSION stays 3; a host that needs paths checks for the symbol.
+ */
+typedef struct mimeo_path_block {
+    uint32_t t, q, len;
+} mimeo_path_block;
+int mimeo_align_units_paths(const mimeo_genome *A, const mimeo_genome *B, const uint32_t *pair_t,
+                            const uint32_t *pair_q, const uint8_t *pair_strand, uint64_t npairs,
+                            const mimeo_params *p, mimeo_alignment **out, uint64_t *nout,
+                            uint64_t **path_first, mimeo_path_block **blocks, uint64_t *nblocks);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  mimeo_last_error() describes the last one.

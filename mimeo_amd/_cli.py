@@ -45,6 +45,12 @@ def add_common(parser, prog, gff_default, label, prefix, with_b):
                              'lastz\'s behaviour; parity unpinned). An error without --anchorRule path.')
 
 
+    parser.add_argument('--paf', type=str, default=None, metavar='FILE',
+                        help='Also write the rows of the alignment file as PAF with their alignments (cg:Z: CIGAR of M/I/D, AS:i: score) '
+                             'to FILE, in the same order. Off by default: without it no path is computed. Ignored with --recycle '
+                             'when the alignment file exists.')
+
+
 def check_common(parser, args):
     """cross-flag rules of add_common (parser.error exits with status 2)"""
     if args.boundExtensions and args.anchorRule != 'path':

@@ -18,7 +18,7 @@ SYMBOLS = [
     'mimeo_genome_length', 'mimeo_seed_hits', 'mimeo_ungapped_hsps', 'mimeo_align_pair', 'mimeo_align_pairs',
     'mimeo_coverage_collapse', 'mimeo_tandem_masked', 'mimeo_genome_load_fasta', 'mimeo_genome_name',
     'mimeo_genome_keep_indexes', 'mimeo_genome_drop_indexes', 'mimeo_genome_build_indexes', 'mimeo_coverage_bedgraph',
-    'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps',
+    'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths',
 ]
 
 
@@ -65,6 +65,7 @@ ALIGNMENT = np.dtype([('tid', '<u4'), ('qid', '<u4'), ('tstart', '<u4'), ('tend'
                       ('qend', '<u4'), ('score', '<i8'), ('id_n', '<u4'), ('id_d', '<u4'), ('qstrand', '<u4'),
                       ('reserved', '<u4')])
 INTERVAL = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4')])
+PATH_BLOCK = np.dtype([('t', '<u4'), ('q', '<u4'), ('len', '<u4')])   # mimeo_path_block
 DEPTH_RUN = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4'), ('depth', '<u4')])
 
 _lib = None
@@ -107,6 +108,9 @@ def load():
     if hasattr(lib, 'mimeo_align_units'):
         lib.mimeo_align_units.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(Params), C.POINTER(vp), C.POINTER(u64)]
         lib.mimeo_get_failed_pairs.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    if hasattr(lib, 'mimeo_align_units_paths'):
+        lib.mimeo_align_units_paths.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(Params), C.POINTER(vp), C.POINTER(u64),
+                                                C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

@@ -365,6 +365,16 @@ int mimeo_align_units(const mimeo_genome *A, const mimeo_genome *B, const uint32
     return align_units_impl(A, B == A ? nullptr : B, pair_t, pair_q, pair_strand, npairs, p, out, nout);
 }
 
+int mimeo_align_units_paths(const mimeo_genome *A, const mimeo_genome *B, const uint32_t *pair_t, const uint32_t *pair_q,
+                            const uint8_t *pair_strand, uint64_t npairs, const mimeo_params *p, mimeo_alignment **out, uint64_t *nout,
+                            uint64_t **path_first, mimeo_path_block **blocks, uint64_t *nblocks) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!A || !p || !out || !nout || !path_first || !blocks || !nblocks || (npairs && (!pair_t || !pair_q))) { set_error("null argument"); return MIMEO_ERR_ARG; }
+    if ((rc = check_params(p))) return rc;
+    return align_units_impl(A, B == A ? nullptr : B, pair_t, pair_q, pair_strand, npairs, p, out, nout, path_first, blocks, nblocks);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

@@ -272,11 +272,15 @@ struct Group {
 int chain_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_hsps, const uint32_t *d_hsp_unit, uint64_t nhsps,
                  int do_chain, mimeo_hsp *d_sorted, long long *d_best, long long *d_cand, int *d_pred, uint32_t *d_order);
 // K6 (k6_gapped.hip): anchors -> gapped alignments; alignments of group g land at
-// d_aln[hsp_begin .. hsp_begin + naln)
+// d_aln[hsp_begin .. hsp_begin + naln).  want_paths: the blocks of every returned alignment are kept for dense_paths_device
+// (box rule: one trace pass after the last round); without it the launches are those of a call that knows no paths
 int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, const uint32_t *d_order,
-                  uint64_t nhsps, const mimeo_params *p, mimeo_alignment *d_aln);
+                  uint64_t nhsps, const mimeo_params *p, mimeo_alignment *d_aln, bool want_paths = false);
 // alignments of all groups packed densely (group g: d_dense[job0 .. job0 + naln)); same stream as gapped_device
 void dense_alignments_device(Group *d_groups, uint32_t ngroups, const mimeo_alignment *d_aln, mimeo_alignment *d_dense);
+// ... and, after gapped_device(want_paths), their paths in the same order: first = ndense + 1 offsets (uint64) into blocks
+// (mimeo_path_block), merged at the anchor
+int dense_paths_device(const Group *d_groups, uint32_t ngroups, uint64_t ndense, DeviceBuf &first, DeviceBuf &blocks, uint64_t *nblocks);
 // ---- super-scaffolds (pack.hip): small scaffolds concatenated behind spacers of N for K2 / K34 / K4 -------------------
 typedef host_plan::Member PackMember;   // scaffold number, first base inside the super-scaffold, bases (host_plan.h)
 struct SuperSide {
@@ -305,7 +309,7 @@ void release_pack_buffers();
 // chain + gapped extension of every group (pipeline.hip)
 int chain_gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_hsps, const uint32_t *d_hsp_unit, uint64_t nhsps,
                         const mimeo_params *p, DeviceBuf &scratch, mimeo_alignment *d_aln, float *ms_chain,
-                        float *ms_gapped);
+                        float *ms_gapped, bool want_paths = false);
 
 // K7: depth runs (bedtools genomecov -bg); host in, host out (in chrom, start order)
 int coverage_bedgraph_device(const mimeo_interval *h_iv, uint64_t n, const uint32_t *h_chrom_len, uint32_t nchrom,
@@ -316,7 +320,8 @@ int coverage_collapse_device(const mimeo_interval *h_iv, uint64_t n, const uint3
 
 // whole-job loop (pipeline.hip): pair k on the strands pair_strand[k] (null: p->strand for every pair)
 int align_units_impl(const mimeo_genome *A, const mimeo_genome *B, const uint32_t *pair_t, const uint32_t *pair_q,
-                     const uint8_t *pair_strand, uint64_t npairs, const mimeo_params *p, mimeo_alignment **out, uint64_t *nout);
+                     const uint8_t *pair_strand, uint64_t npairs, const mimeo_params *p, mimeo_alignment **out, uint64_t *nout,
+                     uint64_t **path_first = nullptr, mimeo_path_block **path_blocks = nullptr, uint64_t *npath_blocks = nullptr);
 // pairs of the last align call that hit a documented limit (their rows are left out, the call goes on): (pair index, code)
 const std::vector<std::pair<uint64_t, int>> &failed_pairs();
 

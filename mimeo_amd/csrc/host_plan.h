@@ -123,6 +123,28 @@ inline MirrorPairs mirror_pairs(const uint32_t *pair_t, const uint32_t *pair_q, 
     return m;
 }
 
+// Rows of one pair as the batches left them -> plus-strand rows first, stable (a pair's strands may come from different
+// batches).  cnt / blk (null: no paths): cnt[i] blocks of row i, all rows' blocks one after the other in blk; they move
+// with their rows.  Row: anything with .qstrand
+template <typename Row, typename Block>
+inline void plus_strand_first(std::vector<Row> &rows, std::vector<uint32_t> *cnt, std::vector<Block> *blk) {
+    auto by_strand = [](const Row &a, const Row &b) { return a.qstrand < b.qstrand; };
+    if (!cnt) { std::stable_sort(rows.begin(), rows.end(), by_strand); return; }
+    if (std::is_sorted(rows.begin(), rows.end(), by_strand)) return;
+    std::vector<size_t> ord(rows.size()), off(rows.size() + 1, 0);
+    for (size_t i = 0; i < rows.size(); i++) { ord[i] = i; off[i + 1] = off[i] + (*cnt)[i]; }
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return rows[a].qstrand < rows[b].qstrand; });
+    std::vector<Row> r2;
+    std::vector<uint32_t> c2;
+    std::vector<Block> b2;
+    r2.reserve(rows.size()); c2.reserve(rows.size()); b2.reserve(blk->size());
+    for (size_t i : ord) {
+        r2.push_back(rows[i]); c2.push_back((*cnt)[i]);
+        b2.insert(b2.end(), blk->begin() + off[i], blk->begin() + off[i + 1]);
+    }
+    rows.swap(r2); cnt->swap(c2); blk->swap(b2);
+}
+
 // Batch cut.  A unit takes one work slot, or two with its mirror rider (which never leaves it); the batch that starts at
 // unit b0 takes units greedily while the slots, the expected seed hits and the group weights stay within the limits — the
 // first unit whatever it costs.

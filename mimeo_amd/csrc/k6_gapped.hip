@@ -31,10 +31,16 @@
 //     nearest earlier path on either side of the anchor's diagonal is dead (alignment specification v1, rule 7; the specification is
 //     tests/bounded_oracle.c).  k6_dp1_bounded / k6_dp_any<true> / k6_trace<true> look the bounds up row range by row range
 //     (bounds_at); k6_resolve<true, true> sends an anchor back when an alignment accepted after its DP ran reaches into what it swept.
+//   * paths out (mimeo_align_units_paths, under every rule; a call that does not ask launches what it launched before): the blocks of
+//     the two halves of every returned alignment, merged at the anchor, in the dense order of k6_dense_copy (k6_path_count, a
+//     scan, k6_path_write).  Under the box rule one trace pass after the last round makes the blocks (paths_pass).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
+
+#include <rocprim/rocprim.hpp>
 
 #include "device_util.h"
 
@@ -308,6 +314,7 @@ __device__ HalfResult wave_half_extend_2048(const GStrandView &T, const GStrandV
 struct PathBlock {
     uint32_t t, q, len;
 };
+static_assert(sizeof(PathBlock) == sizeof(mimeo_path_block), "PathBlock is what mimeo_align_units_paths hands out");
 constexpr uint32_t PATH_UNTRACED = 0xFFFFFFFFu;  // pidx[slot].x of a half whose traceback did not fit the trace pool
 struct PathView {
     const uint2 *pidx;       // per half slot (as HalfResult): first block in blk, block count
@@ -1361,7 +1368,8 @@ __device__ __forceinline__ bool bounds_touch(const PathView &P, const uint2 *anc
 // is accepted, every alignment accepted since is tested against what r's halves swept (bounds_touch); if one touches,
 // the result is stale: the anchor goes back to A_NEW and the group's resolve stops there, so the next round runs it
 // again as the group's lowest unfinalised anchor, which is always bounded by exactly the alignments below it.
-template <bool PATH, bool BOUND = false>
+// RANK (box rule, paths asked for): the rank of every accepted anchor is recorded as under the path rule (k6_kept_jobs).
+template <bool PATH, bool BOUND = false, bool RANK = false>
 __global__ __launch_bounds__(64) void k6_resolve(Group *__restrict__ groups, const uint2 *__restrict__ anchors,
                                                  const HalfResult *__restrict__ res, mimeo_alignment *__restrict__ aln,
                                                  uint8_t *__restrict__ astate, unsigned int *__restrict__ remaining, PathView P,
@@ -1420,7 +1428,8 @@ __global__ __launch_bounds__(64) void k6_resolve(Group *__restrict__ groups, con
             m.id_d = L.nm + R.nm + L.nx + R.nx;
             aln[b0 + nacc0 + nnew] = m;
             sbox[nnew] = make_uint4(m.tstart, m.tend, m.qstart, m.qend);
-            if (PATH) { srank[PATH ? nnew : 0] = r; P.accrank[b0 + nacc0 + nnew] = r; }
+            if (PATH) srank[PATH ? nnew : 0] = r;
+            if (PATH || RANK) P.accrank[b0 + nacc0 + nnew] = r;
             astate[b0 + r] = A_ACCEPTED;
         }
         nnew++;
@@ -1518,6 +1527,7 @@ void dense_alignments_device(Group *d_groups, uint32_t ngroups, const mimeo_alig
 static DeviceBuf g_anchors, g_packed, g_jobs, g_res, g_cnt, g_astate, g_ovf_list, g_any;
 // path rule: per half slot (first block, count), per alignment slot the anchor's rank, the block arena, the trace pool
 static DeviceBuf g_pidx, g_accrank, g_arena, g_pool, g_tjobs, g_tres, g_tctr;
+static DeviceBuf g_kjobs, g_pcnt, g_pslot, g_ptmp;   // paths out: jobs of the box rule's trace pass; block counts, half slots, scan scratch
 static DeviceBuf g_sweep;   // bounded extensions: per half slot what its DP swept (HalfSweep)
 
 // bounded extensions with penalties outside the lean kernel's domain: every job of the round goes to k6_dp_any<true>
@@ -1525,6 +1535,139 @@ __global__ void k6_list_all(uint32_t n, unsigned int *__restrict__ novf, unsigne
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) ovf_list[k] = k;
     if (k == 0) *novf = n;
+}
+
+// ---- paths out (mimeo_align_units_paths) ----------------------------------------------------------------------------------
+// The path of a returned alignment = the blocks of its left half, then those of its right half (both sorted by t, strand
+// coordinates), two consecutive blocks merged when the second continues the first on its diagonal — at the anchor, when both
+// halves leave it diagonally.  Under the path rule every extended half has its blocks already; under the box rule one trace
+// pass after the last round makes those of the alignments that are returned (paths_pass); gap-free mode writes one block per
+// alignment (k6_ungapped_paths).  accrank, compacted as k6_finish compacts the alignments (k6_kept_ranks), names the halves.
+
+// box rule: the two halves of every accepted alignment with score >= thresh, as jobs for k6_trace.  One thread per group;
+// jobs == nullptr: count only (ctr[0]), else the list (ctr[1]: its fill)
+__global__ void k6_kept_jobs(const Group *__restrict__ groups, uint32_t ngroups, const mimeo_alignment *__restrict__ aln,
+                             const uint2 *__restrict__ anchors, const uint32_t *__restrict__ accrank, int32_t thresh,
+                             DpJob *__restrict__ jobs, unsigned int *__restrict__ ctr) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ngroups) return;
+    const Group &G = groups[g];
+    const uint64_t b0 = G.hsp_begin;
+    uint32_t n = 0;
+    for (uint32_t e = 0; e < G.nacc; e++) n += aln[b0 + e].score >= thresh ? 1u : 0u;
+    if (!n) return;
+    if (!jobs) { atomicAdd(&ctr[0], 2u * n); return; }
+    unsigned int j = atomicAdd(&ctr[1], 2u * n);
+    for (uint32_t e = 0; e < G.nacc; e++) {
+        if (aln[b0 + e].score < thresh) continue;
+        const uint32_t rank = accrank[b0 + e];
+        const uint2 a = anchors[b0 + rank];
+        const uint32_t slot = 2u * (uint32_t)(b0 + rank);
+        jobs[j++] = DpJob{g, a.x, a.y, -1, slot, 0};
+        jobs[j++] = DpJob{g, a.x, a.y, +1, slot + 1, 0};
+    }
+}
+
+// before k6_finish: accrank[hsp_begin + k] = anchor rank of the k-th alignment that k6_finish keeps; a kept alignment with a
+// half whose traceback did not fit the trace pool fails its group (what k6_resolve<true> does under the path rule)
+__global__ void k6_kept_ranks(Group *__restrict__ groups, uint32_t ngroups, const mimeo_alignment *__restrict__ aln,
+                              uint32_t *__restrict__ accrank, const uint2 *__restrict__ pidx, int32_t thresh) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ngroups) return;
+    Group &G = groups[g];
+    const uint64_t b0 = G.hsp_begin;
+    uint32_t k = 0;
+    for (uint32_t e = 0; e < G.nacc; e++) {
+        if (aln[b0 + e].score < thresh) continue;
+        const uint32_t rank = accrank[b0 + e];
+        const uint32_t slot = 2u * (uint32_t)(b0 + rank);
+        if (pidx[slot].x == PATH_UNTRACED || pidx[slot + 1].x == PATH_UNTRACED) G.overflow = 1;
+        accrank[b0 + k++] = rank;   // k <= e
+    }
+}
+
+// gap-free mode, after k6_ungapped: alignment r of a group is one block, kept as the left half of "anchor" r
+__global__ __launch_bounds__(256) void k6_ungapped_paths(const Group *__restrict__ groups, const mimeo_alignment *__restrict__ aln,
+                                                         PathBlock *__restrict__ arena, uint2 *__restrict__ pidx,
+                                                         uint32_t *__restrict__ accrank) {
+    const Group &G = groups[blockIdx.x];
+    const uint64_t b0 = G.hsp_begin;
+    for (uint32_t r = threadIdx.x; r < G.nacc; r += 256) {
+        const mimeo_alignment a = aln[b0 + r];
+        arena[b0 + r] = PathBlock{a.tstart, a.qstart, a.tend - a.tstart};
+        pidx[2u * (b0 + r)] = make_uint2((uint32_t)(b0 + r), 1u);
+        pidx[2u * (b0 + r) + 1u] = make_uint2(0u, 0u);
+        accrank[b0 + r] = r;
+    }
+}
+
+// after k6_finish and k6_dense_offsets: the left half slot of every returned alignment, in dense order
+__global__ __launch_bounds__(64) void k6_path_slots(const Group *__restrict__ groups, const uint32_t *__restrict__ accrank,
+                                                    uint32_t *__restrict__ halfslot) {
+    const Group &G = groups[blockIdx.x];
+    for (uint32_t k = threadIdx.x; k < G.naln; k += 64) halfslot[G.job0 + k] = 2u * (uint32_t)(G.hsp_begin + accrank[G.hsp_begin + k]);
+}
+
+// the halves of dense alignment d (an untraced half: no blocks; its group has failed) and block i of the two together
+struct PathHalves { uint2 L, R; };
+__device__ __forceinline__ PathHalves path_halves(const uint32_t *__restrict__ halfslot, const uint2 *__restrict__ pidx, uint32_t d) {
+    const uint32_t hs = halfslot[d];
+    PathHalves H{pidx[hs], pidx[hs + 1u]};
+    if (H.L.x == PATH_UNTRACED) H.L = make_uint2(0u, 0u);
+    if (H.R.x == PATH_UNTRACED) H.R = make_uint2(0u, 0u);
+    return H;
+}
+__device__ __forceinline__ PathBlock path_block(const PathBlock *__restrict__ arena, const PathHalves &H, uint32_t i) {
+    return i < H.L.y ? arena[H.L.x + i] : arena[H.R.x + (i - H.L.y)];
+}
+__device__ __forceinline__ bool path_continues(const PathBlock &a, const PathBlock &b) { return a.t + a.len == b.t && a.q + a.len == b.q; }
+
+// count pass: one wavefront per alignment, lanes stride over its blocks; a block counts unless it continues the one before
+constexpr int PATH_WAVES = 4;
+__global__ __launch_bounds__(64 * PATH_WAVES) void k6_path_count(const uint32_t *__restrict__ halfslot, const uint2 *__restrict__ pidx,
+                                                                 const PathBlock *__restrict__ arena, uint32_t ndense,
+                                                                 uint32_t *__restrict__ cnt) {
+    const uint32_t d = blockIdx.x * PATH_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (d >= ndense) return;   // wave-uniform
+    const PathHalves H = path_halves(halfslot, pidx, d);
+    const uint32_t n = H.L.y + H.R.y;
+    uint32_t c = 0;
+    for (uint32_t i = lane; i < n; i += 64u)
+        if (i == 0 || !path_continues(path_block(arena, H, i - 1u), path_block(arena, H, i))) c++;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if (lane == 0) cnt[d] = c;
+}
+// write pass: alignment d's blocks at out[first[d] ..); the lane of a block that starts an output block adds up the blocks
+// that continue it (at most the two at the anchor, as a half's own blocks never touch)
+__global__ __launch_bounds__(64 * PATH_WAVES) void k6_path_write(const uint32_t *__restrict__ halfslot, const uint2 *__restrict__ pidx,
+                                                                 const PathBlock *__restrict__ arena, uint32_t ndense,
+                                                                 const unsigned long long *__restrict__ first,
+                                                                 PathBlock *__restrict__ out) {
+    const uint32_t d = blockIdx.x * PATH_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (d >= ndense) return;   // wave-uniform
+    const PathHalves H = path_halves(halfslot, pidx, d);
+    const uint32_t n = H.L.y + H.R.y;
+    PathBlock *dst = out + first[d];
+    uint32_t run = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
+        const uint32_t i = i0 + lane;
+        PathBlock b{0, 0, 0};
+        bool start = false;
+        if (i < n) {
+            b = path_block(arena, H, i);
+            start = i == 0 || !path_continues(path_block(arena, H, i - 1u), b);
+        }
+        const uint64_t ball = __ballot(start);
+        if (start) {
+            for (uint32_t j = i + 1u; j < n; j++) {
+                const PathBlock nb = path_block(arena, H, j);
+                if (!path_continues(b, nb)) break;
+                b.len += nb.len;
+            }
+            dst[run + (uint32_t)__popcll(ball & ((1ull << lane) - 1ull))] = b;
+        }
+        run += (uint32_t)__popcll(ball);
+    }
 }
 
 // bytes of traceback the path rule may hold at once: a share of the free device memory (like the queue arenas of K4);
@@ -1551,15 +1694,16 @@ static int arena_reserve(uint64_t blocks, uint64_t used) {
     return 0;
 }
 
-// path rule, after the DP kernels of a round: the traceback of every half of the round's h0 jobs, in slices of jobs whose
+// path rule, after the DP kernels of a round: the traceback of every half of the h0 jobs in d_jobs (the round's; under the box
+// rule with paths asked for, the halves of the alignments that are returned: paths_pass), in slices of jobs whose
 // tracebacks fit the pool together.  A half whose traceback alone exceeds the pool gets no path (PATH_UNTRACED): k6_resolve
 // fails its group if the anchor is accepted, as for a band beyond the DP limit.
-static int trace_round(Group *d_groups, uint32_t h0, const mimeo_params *p, uint64_t budget, uint64_t *arena_used, float *ms,
+static int trace_round(Group *d_groups, const DpJob *d_jobs, uint32_t h0, const mimeo_params *p, uint64_t budget, uint64_t *arena_used, float *ms,
                        uint32_t *slices, uint64_t *largest, bool bounded, BoundCtx bc) {
     hipStream_t st = stream();
     int rc;
     if ((rc = g_tres.reserve((size_t)h0 * sizeof(HalfResult)))) return rc;
-    hipLaunchKernelGGL(k6_trace_gather, dim3((h0 + 255) / 256), dim3(256), 0, st, (const DpJob *)g_jobs.p, h0, (const HalfResult *)g_res.p,
+    hipLaunchKernelGGL(k6_trace_gather, dim3((h0 + 255) / 256), dim3(256), 0, st, d_jobs, h0, (const HalfResult *)g_res.p,
                        (HalfResult *)g_tres.p);
     std::vector<HalfResult> hr(h0);
     HIP_TRY(hipMemcpyAsync(hr.data(), g_tres.p, (size_t)h0 * sizeof(HalfResult), hipMemcpyDeviceToHost, st));
@@ -1607,7 +1751,7 @@ static int trace_round(Group *d_groups, uint32_t h0, const mimeo_params *p, uint
     for (size_t c = 0; c + 1 < cut.size(); c++)
         if (cut[c + 1] > cut[c] && ++*slices)
             hipLaunchKernelGGL(trace, dim3(cut[c + 1] - cut[c]), dim3(TR_THREADS), 0, st, (const Group *)d_groups,
-                               (const DpJob *)g_jobs.p, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
+                               d_jobs, (const TraceJob *)g_tjobs.p, cut[c], (const HalfResult *)g_res.p,
                                (uint8_t *)g_pool.p, (PathBlock *)g_arena.p, (unsigned long long)(g_arena.cap / sizeof(PathBlock)),
                                (uint2 *)g_pidx.p, (unsigned int *)g_tctr.p, O, E, Y, bc);
     HIP_TRY(hipEventRecord(e1, st));
@@ -1700,13 +1844,85 @@ static int round_stats(uint32_t n, uint64_t nhsps, bool bounded, unsigned long l
     return 0;
 }
 
+// after gapped_device(want_paths) and dense_alignments_device: the paths of the ndense dense alignments, in their order.
+// first: ndense + 1 offsets into blocks
+int dense_paths_device(const Group *d_groups, uint32_t ngroups, uint64_t ndense, DeviceBuf &first, DeviceBuf &blocks, uint64_t *nblocks) {
+    hipStream_t st = stream();
+    int rc;
+    *nblocks = 0;
+    if ((rc = first.reserve((size_t)(ndense + 1) * 8))) return rc;
+    if (!ndense) { HIP_TRY(hipMemsetAsync(first.p, 0, 8, st)); return 0; }
+    if (ndense >= (1ull << 32)) { set_error("paths: more than 2^32 alignments in one batch"); return MIMEO_ERR_LIMIT; }
+    if ((rc = g_pcnt.reserve((size_t)(ndense + 1) * 4)) || (rc = g_pslot.reserve((size_t)ndense * 4))) return rc;
+    HIP_TRY(hipMemsetAsync(g_pcnt.p, 0, (size_t)(ndense + 1) * 4, st));
+    const uint32_t nd = (uint32_t)ndense;
+    const dim3 grid((nd + PATH_WAVES - 1) / PATH_WAVES), block(64 * PATH_WAVES);
+    hipLaunchKernelGGL(k6_path_slots, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint32_t *)g_accrank.p, (uint32_t *)g_pslot.p);
+    hipLaunchKernelGGL(k6_path_count, grid, block, 0, st, (const uint32_t *)g_pslot.p, (const uint2 *)g_pidx.p, (const PathBlock *)g_arena.p, nd,
+                       (uint32_t *)g_pcnt.p);
+    size_t tb = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tb, (uint32_t *)g_pcnt.p, (unsigned long long *)first.p, 0ull, (size_t)ndense + 1,
+                                    rocprim::plus<unsigned long long>(), st));
+    if ((rc = g_ptmp.reserve(tb ? tb : 1))) return rc;
+    HIP_TRY(rocprim::exclusive_scan(g_ptmp.p, tb, (uint32_t *)g_pcnt.p, (unsigned long long *)first.p, 0ull, (size_t)ndense + 1,
+                                    rocprim::plus<unsigned long long>(), st));
+    unsigned long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, (const unsigned long long *)first.p + ndense, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *nblocks = total;
+    if (!total) return 0;
+    if ((rc = blocks.reserve((size_t)total * sizeof(PathBlock)))) return rc;
+    hipLaunchKernelGGL(k6_path_write, grid, block, 0, st, (const uint32_t *)g_pslot.p, (const uint2 *)g_pidx.p, (const PathBlock *)g_arena.p, nd,
+                       (const unsigned long long *)first.p, (PathBlock *)blocks.p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// paths out under the box rule, after the last round: one trace pass over the two halves of every accepted alignment with
+// score >= hspthresh (k6_kept_jobs), through the slices of trace_round; k6_trace<false>'s agreement check stays an error
+static int paths_pass(Group *d_groups, uint32_t ngroups, const mimeo_params *p, const mimeo_alignment *d_aln, uint64_t budget,
+                      bool k6_stats) {
+    hipStream_t st = stream();
+    int rc;
+    unsigned int *ctr = (unsigned int *)g_cnt.p;
+    HIP_TRY(hipMemsetAsync(g_cnt.p, 0, 16, st));
+    const dim3 grid((ngroups + 63) / 64), block(64);
+    hipLaunchKernelGGL(k6_kept_jobs, grid, block, 0, st, (const Group *)d_groups, ngroups, d_aln, (const uint2 *)g_anchors.p,
+                       (const uint32_t *)g_accrank.p, p->hspthresh, (DpJob *)nullptr, ctr);
+    unsigned int njobs = 0;
+    HIP_TRY(hipMemcpyAsync(&njobs, ctr, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!njobs) return 0;
+    if ((rc = g_kjobs.reserve((size_t)njobs * sizeof(DpJob)))) return rc;
+    hipLaunchKernelGGL(k6_kept_jobs, grid, block, 0, st, (const Group *)d_groups, ngroups, d_aln, (const uint2 *)g_anchors.p,
+                       (const uint32_t *)g_accrank.p, p->hspthresh, (DpJob *)g_kjobs.p, ctr);
+    uint64_t arena_used = 0, largest = 0;
+    float ms = 0;
+    uint32_t slices = 0;
+    if ((rc = trace_round(d_groups, (const DpJob *)g_kjobs.p, njobs, p, budget, &arena_used, &ms, &slices, &largest, false, BoundCtx{}))) return rc;
+    if (k6_stats)
+        fprintf(stderr, "[k6] paths out: traceback of %u halves %.3f ms, slices %u, %llu path blocks, pool %.1f MB, largest half %.3f MB\n", njobs, ms,
+                slices, (unsigned long long)arena_used, g_pool.cap / 1048576.0, largest / 1048576.0);
+    return 0;
+}
+
 int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, const uint32_t *d_order,
-                  uint64_t nhsps, const mimeo_params *p, mimeo_alignment *d_aln) {
+                  uint64_t nhsps, const mimeo_params *p, mimeo_alignment *d_aln, bool want_paths) {
     if (!ngroups || !nhsps) return 0;
     hipStream_t st = stream();
     int rc;
+    if (want_paths) {   // per half slot its blocks, per alignment slot its anchor's rank (the path rule's tables, under every rule)
+        if (nhsps >= (1ull << 31)) { set_error("paths: more than 2^31 HSPs in one batch"); return MIMEO_ERR_LIMIT; }
+        if ((rc = g_pidx.reserve((size_t)nhsps * 2 * sizeof(uint2)))) return rc;
+        if ((rc = g_accrank.reserve((size_t)nhsps * 4))) return rc;
+    }
     if (!p->gapped) {
         hipLaunchKernelGGL(k6_ungapped, dim3(ngroups), dim3(256), 0, st, d_groups, d_sorted, d_order, d_aln);
+        if (want_paths) {
+            if ((rc = arena_reserve(nhsps, 0))) return rc;
+            hipLaunchKernelGGL(k6_ungapped_paths, dim3(ngroups), dim3(256), 0, st, (const Group *)d_groups, (const mimeo_alignment *)d_aln,
+                               (PathBlock *)g_arena.p, (uint2 *)g_pidx.p, (uint32_t *)g_accrank.p);
+        }
     } else {
         // development switches: read once per call, not per round (MIMEO_K6_TRACE_POOL_MB: trace_pool_budget)
         uint32_t bmax = 8192u / ngroups;  // anchors per group and round (200 units: 32 -> one large round and a short one)
@@ -1739,7 +1955,8 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
         uint32_t trace_slices = 0, rounds = 0;
         uint64_t largest = 0;   // largest traceback of one half (bytes)
         PathView pv{nullptr, nullptr, nullptr};
-        if (path) {
+        const bool box_paths = want_paths && !path;   // the anchors' ranks are recorded; the halves are traced after the last round
+        if (path || box_paths) {
             if ((rc = g_pidx.reserve((size_t)nhsps * 2 * sizeof(uint2)))) return rc;
             if ((rc = g_accrank.reserve((size_t)nhsps * 4))) return rc;
             if ((rc = g_tctr.reserve(16))) return rc;
@@ -1750,7 +1967,8 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
         }
         if (bounded && (rc = g_sweep.reserve((size_t)nhsps * 2 * sizeof(HalfSweep)))) return rc;
         const auto pick = path ? k6_pick<true> : k6_pick<false>;
-        const auto resolve = bounded ? k6_resolve<true, true> : path ? k6_resolve<true, false> : k6_resolve<false, false>;
+        const auto resolve = bounded ? k6_resolve<true, true> : path ? k6_resolve<true, false>
+                             : box_paths ? k6_resolve<false, false, true> : k6_resolve<false, false>;
         const HalfSweep *sweep = bounded ? (const HalfSweep *)g_sweep.p : nullptr;
         for (;;) {
             HIP_TRY(hipMemsetAsync(g_cnt.p, 0, 16, st));
@@ -1767,7 +1985,7 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
                 if (k6_stats && (rc = round_stats(h0, nhsps, bounded, &bound_jobs))) return rc;
                 if (path) {
                     rounds++;
-                    if ((rc = trace_round(d_groups, h0, p, pool_budget, &arena_used, &ms_trace, &trace_slices, &largest, bounded, bc))) return rc;
+                    if ((rc = trace_round(d_groups, (const DpJob *)g_jobs.p, h0, p, pool_budget, &arena_used, &ms_trace, &trace_slices, &largest, bounded, bc))) return rc;
                     pv.blk = (const PathBlock *)g_arena.p;
                 }
             }
@@ -1785,7 +2003,11 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
             if (bounded) fprintf(stderr, ", bounded jobs %llu, rescheduled %llu", bound_jobs, rescheduled);
             fprintf(stderr, "\n");
         }
+        if (box_paths && (rc = paths_pass(d_groups, ngroups, p, d_aln, pool_budget, k6_stats))) return rc;
     }
+    if (want_paths)
+        hipLaunchKernelGGL(k6_kept_ranks, dim3((ngroups + 63) / 64), dim3(64), 0, st, d_groups, ngroups, (const mimeo_alignment *)d_aln,
+                           (uint32_t *)g_accrank.p, (const uint2 *)g_pidx.p, p->hspthresh);
     hipLaunchKernelGGL(k6_finish, dim3((ngroups + 63) / 64), dim3(64), 0, st, d_groups, ngroups, d_aln, p->hspthresh);
     HIP_TRY(hipGetLastError());
     return 0;

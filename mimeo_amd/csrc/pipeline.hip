@@ -97,6 +97,7 @@ struct IndexCache {
 
 static ExtBatch g_ext;
 static DeviceBuf g_scratch, g_aln, g_dense, g_groups;
+static DeviceBuf g_pfirst, g_pblocks;   // paths of the batch's dense alignments (dense_paths_device)
 // device tables of the packed path (run_packed)
 static struct PackTables {
     DeviceBuf toff, tstart, tlen, trank, qoff, qstart, qlen, qrank, pairidx, pt, pq, tview, qvf, qvr, utab;
@@ -153,7 +154,7 @@ struct Switches {
 // mimeo_shutdown: give the work buffers and streams back
 void release_pipeline_buffers() {
     g_ext.release();
-    for (DeviceBuf *b : {&g_scratch, &g_aln, &g_dense, &g_groups}) b->release();
+    for (DeviceBuf *b : {&g_scratch, &g_aln, &g_dense, &g_groups, &g_pfirst, &g_pblocks}) b->release();
     g_pack.release();
     release_pack_buffers();
 }
@@ -197,11 +198,24 @@ static void record_failure(uint64_t pair, uint32_t tid, uint32_t qid, char stran
 
 // ---- the batch driver ------------------------------------------------------------------------------------------------------
 struct CallTimes { ExtStats est; float ms_chain = 0, ms_gapped = 0, ms_index = 0; };
+// mimeo_align_units_paths: the paths travel next to the alignments — per batch in dense order, then per pair
+struct PairPaths {
+    std::vector<uint64_t> first;               // of the batch at hand: offsets of its dense alignments into dense (one more than alignments)
+    std::vector<mimeo_path_block> dense;
+    std::vector<std::vector<uint32_t>> cnt;            // per pair: blocks of each of its alignments, in the order of its rows
+    std::vector<std::vector<mimeo_path_block>> blk;    // per pair: the blocks, alignment after alignment
+    // dense alignments [d0, d1) of the batch go to `pair`
+    void take(uint64_t pair, uint64_t d0, uint64_t d1) {
+        for (uint64_t d = d0; d < d1; d++) cnt[pair].push_back((uint32_t)(first[d + 1] - first[d]));
+        blk[pair].insert(blk[pair].end(), dense.begin() + first[d0], dense.begin() + first[d1]);
+    }
+};
 // what differs between the per-pair path and the packed path
 struct BatchPath {
     const mimeo_genome *t_owner, *q_owner;   // the genomes whose kept indexes are adopted and that keep new ones (null: supers)
     const Scaffold *tscaf, *qscaf;           // what Unit::t and Unit::q number
     uint64_t *slots_stat;                    // the field of g_stats that counts the path's work slots
+    PairPaths *paths;                        // null: the call asks for no paths
     std::function<uint64_t(const Unit &)> group_bound;   // most groups the unit (with its rider) can yield
     // the groups of the batch (K5 / K6: one per scaffold pair and strand) into g_groups
     std::function<int(const std::vector<Slot> &, const std::vector<UnitWork> &, uint64_t nh, uint32_t *ngroups)> groups_to_device;
@@ -215,6 +229,23 @@ static int read_alignments(const Group &last, std::vector<mimeo_alignment> &host
     host_aln.resize((uint64_t)last.job0 + last.naln);
     if (host_aln.empty()) return 0;
     HIP_TRY(hipMemcpyAsync(host_aln.data(), g_dense.p, host_aln.size() * sizeof(mimeo_alignment), hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+// ... and their paths (only when asked for): emitted on the device in dense order, then read
+static int read_paths(uint32_t ngroups, PairPaths &pp) {
+    Group last;
+    HIP_TRY(hipMemcpyAsync(&last, (const Group *)g_groups.p + (ngroups - 1), sizeof(Group), hipMemcpyDeviceToHost, stream()));
+    HIP_TRY(hipStreamSynchronize(stream()));
+    const uint64_t ndense = (uint64_t)last.job0 + last.naln;
+    uint64_t nblocks = 0;
+    int rc = dense_paths_device((const Group *)g_groups.p, ngroups, ndense, g_pfirst, g_pblocks, &nblocks);
+    if (rc) return rc;
+    pp.first.resize(ndense + 1);
+    pp.dense.resize(nblocks);
+    HIP_TRY(hipMemcpyAsync(pp.first.data(), g_pfirst.p, pp.first.size() * 8, hipMemcpyDeviceToHost, stream()));
+    if (nblocks) HIP_TRY(hipMemcpyAsync(pp.dense.data(), g_pblocks.p, nblocks * sizeof(mimeo_path_block), hipMemcpyDeviceToHost, stream()));
     HIP_TRY(hipStreamSynchronize(stream()));
     return 0;
 }
@@ -303,9 +334,10 @@ static int run_batches(std::vector<Unit> &units, const std::vector<uint64_t> &t_
                 if (ngroups) {
                     if ((rc = g_aln.reserve(nh * sizeof(mimeo_alignment))) || (rc = g_dense.reserve(nh * sizeof(mimeo_alignment)))) return rc;
                     if ((rc = chain_gapped_device((Group *)g_groups.p, ngroups, (const mimeo_hsp *)g_ext.hsps.p, (const uint32_t *)g_ext.hsp_unit.p, nh, p,
-                                                  g_scratch, (mimeo_alignment *)g_aln.p, &tm.ms_chain, &tm.ms_gapped)))
+                                                  g_scratch, (mimeo_alignment *)g_aln.p, &tm.ms_chain, &tm.ms_gapped, path.paths != nullptr)))
                         return rc;
                     dense_alignments_device((Group *)g_groups.p, ngroups, (const mimeo_alignment *)g_aln.p, (mimeo_alignment *)g_dense.p);
+                    if (path.paths && (rc = read_paths(ngroups, *path.paths))) return rc;
                     if (sw.k6_stats && (rc = print_groups(ngroups))) return rc;
                     if ((rc = path.collect(slots, ngroups))) return rc;
                 }
@@ -337,7 +369,7 @@ static int run_batches(std::vector<Unit> &units, const std::vector<uint64_t> &t_
 // *used = false: the caller runs the unit-per-pair path.
 static int run_packed(const mimeo_genome *A, const mimeo_genome *QG, const uint32_t *pair_t, const uint32_t *pair_q, uint64_t npairs,
                       const mimeo_params *p, const Switches &sw, std::vector<std::vector<mimeo_alignment>> &per_pair, std::vector<char> &failed,
-                      CallTimes &tm, bool *used) {
+                      PairPaths *pp, CallTimes &tm, bool *used) {
     *used = false;
     if (!sw.pack) return 0;
     if (npairs == 0 || npairs >= (1ull << 30)) return 0;
@@ -428,7 +460,7 @@ static int run_packed(const mimeo_genome *A, const mimeo_genome *QG, const uint3
                 units.push_back(Unit{{ts, qs, minus, NO_PAIR}, mirrored, NO_PAIR});
             }
     std::vector<uint3> utab;   // of the batch at hand
-    BatchPath path{nullptr, nullptr, ST.supers.data(), SQ.supers.data(), &g_stats.super_units, {}, {}, {}};
+    BatchPath path{nullptr, nullptr, ST.supers.data(), SQ.supers.data(), &g_stats.super_units, pp, {}, {}, {}};
     // groups of a unit: at most (target members named) x nq x 2 (an upper bound; a mirror unit names the other super's)
     path.group_bound = [&](const Unit &u) { return (uint64_t)(ST.members[u.t].size() + (u.mirrored ? ST.members[u.q].size() : 0)) * nq * 2; };
     // every HSP back to its scaffold pair: the groups are made on the device
@@ -457,20 +489,29 @@ static int run_packed(const mimeo_genome *A, const mimeo_genome *QG, const uint3
         std::vector<mimeo_alignment> host_aln;
         if ((rc = read_alignments(last, host_aln))) return rc;
         // dense order = (pair, strand) order: a pair's plus-strand alignments come before its minus-strand ones, as on the other path
-        for (const mimeo_alignment &a : host_aln) per_pair[pairidx[(size_t)trank[a.tid] * nq + qrank[a.qid]]].push_back(a);
+        for (size_t d = 0; d < host_aln.size(); d++) {
+            const mimeo_alignment &a = host_aln[d];
+            const uint32_t pair = pairidx[(size_t)trank[a.tid] * nq + qrank[a.qid]];
+            per_pair[pair].push_back(a);
+            if (pp) pp->take(pair, d, d + 1);
+        }
         return 0;
     };
     rc = run_batches(units, t_bytes, q_bytes, idx_budget, sw.max_units(max_t, max_q), path, p, sw, tm);
     g_stats.pair_strands += cp.distinct * qroles;
     if (!rc)   // duplicates (duplicate, first occurrence) are answered from the first
-        for (auto &dp : cp.dups) { per_pair[dp.first] = per_pair[dp.second]; if (failed[dp.second]) failed[dp.first] = 1; }
+        for (auto &dp : cp.dups) {
+            per_pair[dp.first] = per_pair[dp.second];
+            if (pp) { pp->cnt[dp.first] = pp->cnt[dp.second]; pp->blk[dp.first] = pp->blk[dp.second]; }
+            if (failed[dp.second]) failed[dp.first] = 1;
+        }
     return rc;
 }
 
 // ---- one unit per scaffold pair and strand ---------------------------------------------------------------------------------
 static int run_per_pair(const mimeo_genome *A, const mimeo_genome *QG, const uint32_t *pair_t, const uint32_t *pair_q, const std::vector<uint8_t> &strands,
                         const mimeo_params *p, const Switches &sw, std::vector<std::vector<mimeo_alignment>> &per_pair, std::vector<char> &failed,
-                        CallTimes &tm) {
+                        PairPaths *pp, CallTimes &tm) {
     const uint64_t npairs = strands.size();
     HIP_TRY(hipStreamSynchronize(stream()));   // what run_packed may have started before it declined
     // units in target-major order (stable in the caller's pair order): neighbouring units share the target index
@@ -515,7 +556,7 @@ static int run_per_pair(const mimeo_genome *A, const mimeo_genome *QG, const uin
     int rc = sw.index_budget(&budget);
     if (rc) return rc;
     std::vector<Group> groups;   // of the batch at hand, as uploaded and as K6 left them
-    BatchPath path{A, QG, A->scaf.data(), QG->scaf.data(), &g_stats.pair_strands, {}, {}, {}};
+    BatchPath path{A, QG, A->scaf.data(), QG->scaf.data(), &g_stats.pair_strands, pp, {}, {}, {}};
     path.group_bound = [](const Unit &u) { return (uint64_t)(u.mirrored ? 2 : 1); };   // a group per work slot
     path.groups_to_device = [&](const std::vector<Slot> &slots, const std::vector<UnitWork> &work, uint64_t, uint32_t *ngroups) -> int {
         groups.resize(slots.size());
@@ -545,6 +586,7 @@ static int run_per_pair(const mimeo_genome *A, const mimeo_genome *QG, const uin
             g_stats.chained_hsps += g.nchain;
             auto &dst = per_pair[slots[gi].pair];
             dst.insert(dst.end(), host_aln.begin() + g.job0, host_aln.begin() + g.job0 + g.naln);
+            if (pp) pp->take(slots[gi].pair, g.job0, (uint64_t)g.job0 + g.naln);
         }
         return 0;
     };
@@ -552,7 +594,8 @@ static int run_per_pair(const mimeo_genome *A, const mimeo_genome *QG, const uin
 }
 
 int align_units_impl(const mimeo_genome *A, const mimeo_genome *B, const uint32_t *pair_t, const uint32_t *pair_q, const uint8_t *pair_strand,
-                     uint64_t npairs, const mimeo_params *p, mimeo_alignment **out, uint64_t *nout) {
+                     uint64_t npairs, const mimeo_params *p, mimeo_alignment **out, uint64_t *nout, uint64_t **path_first,
+                     mimeo_path_block **path_blocks, uint64_t *npath_blocks) {
     auto t0 = std::chrono::steady_clock::now();
     memset(&g_stats, 0, sizeof g_stats);
     g_failed.clear();
@@ -572,24 +615,43 @@ int align_units_impl(const mimeo_genome *A, const mimeo_genome *B, const uint32_
     CallTimes tm;
     int rc = 0;
     bool packed = false;
+    PairPaths paths, *pp = path_first ? &paths : nullptr;
+    if (pp) { pp->cnt.resize(npairs); pp->blk.resize(npairs); }
     HIP_TRY(hipStreamSynchronize(stream()));
     if (uniform && npairs) {
-        mimeo_params pp = *p;
-        pp.strand = (int32_t)strands[0];
-        if (pp.strand && (rc = run_packed(A, QG, pair_t, pair_q, npairs, &pp, sw, per_pair, failed, tm, &packed))) return rc;
+        mimeo_params ps = *p;
+        ps.strand = (int32_t)strands[0];
+        if (ps.strand && (rc = run_packed(A, QG, pair_t, pair_q, npairs, &ps, sw, per_pair, failed, pp, tm, &packed))) return rc;
     }
-    if (!packed && (rc = run_per_pair(A, QG, pair_t, pair_q, strands, p, sw, per_pair, failed, tm))) return rc;
+    if (!packed && (rc = run_per_pair(A, QG, pair_t, pair_q, strands, p, sw, per_pair, failed, pp, tm))) return rc;
     for (uint64_t k = 0; k < npairs; k++)
-        if (failed[k]) per_pair[k].clear();   // a pair that hit a limit on one strand yields no rows at all (its lastz run failed)
+        if (failed[k]) {   // a pair that hit a limit on one strand yields no rows at all (its lastz run failed)
+            per_pair[k].clear();
+            if (pp) { pp->cnt[k].clear(); pp->blk[k].clear(); }
+        }
     // a pair's plus-strand alignments come before its minus-strand ones whichever batch made them
-    for (auto &v : per_pair)
-        std::stable_sort(v.begin(), v.end(), [](const mimeo_alignment &a, const mimeo_alignment &b) { return a.qstrand < b.qstrand; });
-    uint64_t total = 0;
+    for (uint64_t k = 0; k < npairs; k++)
+        host_plan::plus_strand_first(per_pair[k], pp ? &pp->cnt[k] : nullptr, pp ? &pp->blk[k] : (std::vector<mimeo_path_block> *)nullptr);
+    uint64_t total = 0, total_blocks = 0;
     for (auto &v : per_pair) total += v.size();
+    if (pp) for (auto &v : pp->blk) total_blocks += v.size();
     mimeo_alignment *res = (mimeo_alignment *)malloc((total ? total : 1) * sizeof(mimeo_alignment));
-    if (!res) { set_error("host allocation failed"); return MIMEO_ERR_NOMEM; }
+    uint64_t *pfirst = pp ? (uint64_t *)malloc((total + 1) * sizeof(uint64_t)) : nullptr;
+    mimeo_path_block *pblk = pp ? (mimeo_path_block *)malloc((total_blocks ? total_blocks : 1) * sizeof(mimeo_path_block)) : nullptr;
+    if (!res || (pp && (!pfirst || !pblk))) { free(res); free(pfirst); free(pblk); set_error("host allocation failed"); return MIMEO_ERR_NOMEM; }
     uint64_t w = 0;
     for (auto &v : per_pair) { if (!v.empty()) memcpy(res + w, v.data(), v.size() * sizeof(mimeo_alignment)); w += v.size(); }
+    if (pp) {   // in the order of the records
+        uint64_t r = 0, b = 0;
+        for (uint64_t k = 0; k < npairs; k++) {
+            for (uint32_t c : pp->cnt[k]) { pfirst[r++] = b; b += c; }
+            if (!pp->blk[k].empty()) memcpy(pblk + (b - pp->blk[k].size()), pp->blk[k].data(), pp->blk[k].size() * sizeof(mimeo_path_block));
+        }
+        pfirst[r] = b;
+        *path_first = pfirst;
+        *path_blocks = pblk;
+        *npath_blocks = total_blocks;
+    }
     *out = res;
     *nout = total;
     const ExtStats &est = tm.est;
@@ -638,7 +700,7 @@ int build_kept_indexes(mimeo_genome *g, const uint32_t *scaf, uint64_t n) {
 
 int chain_gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_hsps, const uint32_t *d_hsp_unit, uint64_t nhsps,
                         const mimeo_params *p, DeviceBuf &scratch, mimeo_alignment *d_aln, float *ms_chain,
-                        float *ms_gapped) {
+                        float *ms_gapped, bool want_paths) {
     if (!ngroups || !nhsps) return 0;
     hipStream_t st = stream();
     // scratch: sorted HSPs | best | cand | pred | order
@@ -655,7 +717,7 @@ int chain_gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_hs
         return rc;
     HIP_TRY(hipEventRecord(e1, st));
     if ((rc = gapped_device(d_groups, ngroups, (const mimeo_hsp *)(b + off_hs), (const uint32_t *)(b + off_order), nhsps, p,
-                            d_aln)))
+                            d_aln, want_paths)))
         return rc;
     HIP_TRY(hipEventRecord(e2, st));
     HIP_TRY(hipStreamSynchronize(st));

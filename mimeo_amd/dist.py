@@ -71,7 +71,7 @@ class Dist:
         return int(t.item())
 
     def allgather_records(self, arr):
-        """Concatenate a structured numpy array over ranks, in rank order, on every rank."""
+        """Concatenate a numpy array (structured or plain) over ranks, in rank order, on every rank."""
         if not self.active:
             return arr
         import torch.distributed as td
@@ -89,6 +89,17 @@ class Dist:
         td.all_gather(outs, buf)
         parts = [o[:s].cpu().numpy().view(arr.dtype) for o, s in zip(outs, sizes)]
         return np.concatenate(parts) if parts else arr
+
+
+    def allgather_paths(self, first, blocks):
+        """The paths that go with allgather_records' records: every rank's block counts and blocks through the same
+        all-gatherv, in rank order; returns (first, blocks) of the concatenation."""
+        if not self.active:
+            return first, blocks
+        cnt = self.allgather_records(np.diff(np.asarray(first, dtype=np.uint64)))
+        out = np.zeros(cnt.size + 1, dtype=np.uint64)
+        out[1:] = np.cumsum(cnt, dtype=np.uint64)
+        return out, self.allgather_records(blocks)
 
 
 def shard_pairs_by_target(pairs, cost_of_target, world, rank):

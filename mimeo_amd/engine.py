@@ -139,25 +139,41 @@ def align_pair(T, tid, Q, qid, params=None):
     return _ffi.take(ptr, n, _ffi.ALIGNMENT)
 
 
-def align_pairs(A, B, pairs, params=None):
-    """pairs: iterable of (target index in A, query index in B or A)."""
+def _align_paths(A, B, pt, pq, ps, p):
+    """mimeo_align_units_paths: (records, first, blocks) — alignment i is blocks[first[i]:first[i + 1]]."""
+    ptr, n, pf, pb, nb = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _ffi.check(_ffi.load().mimeo_align_units_paths(A._h, B._h if B is not None else None, pt.ctypes.data, pq.ctypes.data,
+                                                   ps.ctypes.data if ps is not None else None, len(pt), C.byref(p),
+                                                   C.byref(ptr), C.byref(n), C.byref(pf), C.byref(pb), C.byref(nb)))
+    n1 = C.c_uint64(n.value + 1)
+    return _ffi.take(ptr, n, _ffi.ALIGNMENT), _ffi.take(pf, n1, np.dtype('<u8')), _ffi.take(pb, nb, _ffi.PATH_BLOCK)
+
+
+def align_pairs(A, B, pairs, params=None, paths=False):
+    """pairs: iterable of (target index in A, query index in B or A).  paths=True: (records, first, blocks) with the path of
+    record i as the gap-free blocks blocks[first[i]:first[i + 1]] (_ffi.PATH_BLOCK; include/mimeo_hip.h has the coordinates)."""
     p = params or default_params()
     pr = np.asarray(list(pairs), dtype=np.uint32).reshape(-1, 2)
     pt = np.ascontiguousarray(pr[:, 0])
     pq = np.ascontiguousarray(pr[:, 1])
+    if paths:
+        return _align_paths(A, B, pt, pq, None, p)
     ptr, n = C.c_void_p(), C.c_uint64()
     _ffi.check(_ffi.load().mimeo_align_pairs(A._h, B._h if B is not None else None, pt.ctypes.data, pq.ctypes.data,
                                              len(pt), C.byref(p), C.byref(ptr), C.byref(n)))
     return _ffi.take(ptr, n, _ffi.ALIGNMENT)
 
 
-def align_units(A, B, units, params=None):
+def align_units(A, B, units, params=None, paths=False):
     """units: iterable of (target index in A, query index in B or A, strands) with strands = 1 plus, 2 minus, 3 both
-    (masked with params.strand): mimeo_align_units — a rank's share of a sharded self job (dist.deal_units)."""
+    (masked with params.strand): mimeo_align_units — a rank's share of a sharded self job (dist.deal_units).
+    paths=True: (records, first, blocks), as align_pairs."""
     p = params or default_params()
     un = np.asarray(list(units), dtype=np.uint32).reshape(-1, 3)
     pt, pq = np.ascontiguousarray(un[:, 0]), np.ascontiguousarray(un[:, 1])
     ps = np.ascontiguousarray(un[:, 2].astype(np.uint8))
+    if paths:
+        return _align_paths(A, B, pt, pq, ps, p)
     ptr, n = C.c_void_p(), C.c_uint64()
     _ffi.check(_ffi.load().mimeo_align_units(A._h, B._h if B is not None else None, pt.ctypes.data, pq.ctypes.data, ps.ctypes.data,
                                              len(pt), C.byref(p), C.byref(ptr), C.byref(n)))

@@ -86,14 +86,17 @@ def printed_tenths(id_n, id_d):
     return tenths
 
 
-def tab_blocks(alns, tnames, qnames, min_len, min_idt):
+def tab_blocks(alns, tnames, qnames, min_len, min_idt, rows=None):
     """Every pair's block of the 10-column TAB at once (wrappers.py:1043-1056, per pair:
     awk '0+$5 >= minLen' | awk '0+$13 >= minIdt {print $1,$2,$3,$4,$6,$7,$8,$9,$11,$13}' | sort -k 1,1 -k 3n,4n).
     `alns`: engine records of any number of (target, query) pairs; start1 and start2+ are origin-one (lastz general
     format), ends inclusive == half-open end.  Returns ({(tid, qid): [lines]}, kept) where `kept` is an (n, 4)
     int64 array of (tid, qid, start1, end1) of the rows written, in block order — what the BED projection of the
     file would read back (wrappers.py:1120-1128).  One pass over numpy columns instead of a Python loop per record:
-    a C4 job has 6e5 alignments."""
+    a C4 job has 6e5 alignments.  `rows` (a list, optional) receives one int64 array: the index into `alns` of every row
+    written, in block order (the PAF writer pairs each TAB row with its path)."""
+    if rows is not None:
+        rows.append(np.zeros(0, dtype=np.int64))
     if alns.size == 0:
         return {}, np.zeros((0, 4), dtype=np.int64)
     ts, te = alns['tstart'].astype(np.int64), alns['tend'].astype(np.int64)
@@ -124,11 +127,61 @@ def tab_blocks(alns, tnames, qnames, min_len, min_idt):
             lines[a:b] = [lines[k] for k in o]
             perm[a:b] = o
         idx, tid, qid, s1 = idx[perm], tid[perm], qid[perm], s1[perm]
+    if rows is not None:
+        rows[-1] = idx
     cuts = np.flatnonzero(np.diff(pair)) + 1
     blocks = {}
     for a, b in zip(np.r_[0, cuts].tolist(), np.r_[cuts, pair.size].tolist()):
         blocks[(int(tid[a]), int(qid[a]))] = lines[a:b]
     return blocks, np.stack([tid, qid, s1, te[idx]], axis=1)
+
+
+def cigar(blocks):
+    """The gap-free blocks (t, q, len) of ONE alignment (engine.align_units(..., paths=True)) as a CIGAR of M / I / D with the
+    target as the reference, the SAM convention: M a block, I query bases absent from the target, D target bases absent from
+    the query.  Where both sequences jump between two blocks (an insertion next to a deletion) the I comes first.  No = / X:
+    those need the sequence text."""
+    ops = []
+    for k in range(len(blocks)):
+        b = blocks[k]
+        if k:
+            p = blocks[k - 1]
+            dq, dt = int(b['q']) - int(p['q']) - int(p['len']), int(b['t']) - int(p['t']) - int(p['len'])
+            if dq:
+                ops.append('%dI' % dq)
+            if dt:
+                ops.append('%dD' % dt)
+        ops.append('%dM' % int(b['len']))
+    return ''.join(ops)
+
+
+def select_paths(first, blocks, rows):
+    """(first, blocks) of the alignments `rows` (indexes), in that order"""
+    first = np.asarray(first, dtype=np.int64)
+    rows = np.asarray(rows, dtype=np.int64)
+    cnt = first[rows + 1] - first[rows] if rows.size else np.zeros(0, np.int64)
+    out = np.zeros(rows.size + 1, dtype=np.uint64)
+    out[1:] = np.cumsum(cnt)
+    take = np.repeat(first[rows] - out[:-1].astype(np.int64), cnt) + np.arange(int(out[-1]), dtype=np.int64) if rows.size else np.zeros(0, np.int64)
+    return out, blocks[take]
+
+
+def paf_lines(records, first, blocks, tnames, tlens, qnames, qlens):
+    """One PAF row per record: query name, length, start, end (0-based half-open, query plus strand), strand, target name,
+    length, start, end, residue matches (id_n), alignment length (id_d + gap bases), 255 (no mapping quality), then
+    AS:i:<score> and cg:Z:<cigar>.  The path of record i is blocks[first[i]:first[i + 1]] (mimeo_hip.h,
+    mimeo_align_units_paths): t on the target plus strand, q on the aligned strand, so the CIGAR of a '-' row runs along the
+    target forward and the reverse-complemented query — PAF's own meaning."""
+    lines = []
+    for i in range(len(records)):
+        r = records[i]
+        b = blocks[int(first[i]):int(first[i + 1])]
+        gaps = (int(r['tend']) - int(r['tstart']) - int(r['id_d'])) + (int(r['qend']) - int(r['qstart']) - int(r['id_d']))
+        t, q = int(r['tid']), int(r['qid'])
+        lines.append('%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tcg:Z:%s' % (
+            qnames[q], int(qlens[q]), int(r['qstart']), int(r['qend']), '-' if int(r['qstrand']) else '+', tnames[t], int(tlens[t]),
+            int(r['tstart']), int(r['tend']), int(r['id_n']), int(r['id_d']) + gaps, int(r['score']), cigar(b)))
+    return lines
 
 
 def tab_block(alns, tname, qname, min_len, min_idt):

@@ -45,7 +45,7 @@ PACK_MEMBER_BP = 6 << 20   # the engine packs scaffolds of up to this size into 
 PACK_MIN = 8               # ... this many of them (mimeo_hip.h, mimeo_align_pairs)
 
 
-def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None):
+def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False):
     """Align every pair (sharded over ranks when dist.world > 1) and return {(t, q): [TAB lines]} on every rank, the raw
     record count and the (n, 4) array of (tid, qid, start1, end1) of the rows kept — what the BED projection of the TAB reads
     back (wrappers.py:1120-1128).
@@ -54,8 +54,19 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None):
     scaffolds deals UNITS (dist.deal_units): a rank gets its target rows' minus-strand units and the plus-strand units of the
     unordered pairs dealt to those rows, in both orders, so that the engine computes each plus-strand pair once.  Fragmented
     assemblies (the engine packs them into super-scaffolds when it is handed a full cross product) and two-genome jobs are
-    sharded by target with whole pairs, as before."""
+    sharded by target with whole pairs, as before.
+
+    paths=True (--paf): the engine also returns every alignment's path, the block counts and the blocks travel through the
+    same all-gatherv as the records, and a fourth value comes back: {(t, q): [PAF lines]}, the rows of the TAB blocks in
+    their order."""
     dist = dist or Dist()
+    none = (np.zeros(0, dtype=engine._ffi.ALIGNMENT), np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=engine._ffi.PATH_BLOCK))
+    first = blk = None
+
+    def run(fn, work):
+        if not work:
+            return none if paths else none[0]
+        return fn(A, B, work, params, paths=True) if paths else fn(A, B, work, params)
     QG = B if B is not None else A
     n = len(A.names)
     failed = []
@@ -65,7 +76,7 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None):
         if full_self and small < PACK_MIN:
             cost = {t: A.lengths[t] * sum(A.lengths) for t in range(n)}
             units = deal_units(n, cost, dist.world, dist.rank)
-            alns = engine.align_units(A, None, units, params) if units else np.zeros(0, dtype=engine._ffi.ALIGNMENT)
+            alns = run(engine.align_units, units)
             failed = [(units[i][0], units[i][1]) for i, _ in engine.failed_pairs()] if units else []
         else:
             qsum = {}
@@ -73,17 +84,42 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None):
                 qsum[t] = qsum.get(t, 0) + QG.lengths[q]
             cost = {t: A.lengths[t] * s for t, s in qsum.items()}
             mine = shard_pairs_by_target(pairs, cost, dist.world, dist.rank)
-            alns = engine.align_pairs(A, B, mine, params) if mine else np.zeros(0, dtype=engine._ffi.ALIGNMENT)
+            alns = run(engine.align_pairs, mine)
             failed = [mine[i] for i, _ in engine.failed_pairs()] if mine else []
     else:
         mine = list(pairs)
-        alns = engine.align_pairs(A, B, mine, params) if mine else np.zeros(0, dtype=engine._ffi.ALIGNMENT)
+        alns = run(engine.align_pairs, mine)
         failed = [mine[i] for i, _ in engine.failed_pairs()] if mine else []
     for t, q in failed:   # the reference's script loses a failing lastz run's rows and goes on (utils.py:125-128)
         logging.warning('Alignment of %s onto %s hit an engine limit and was left out: %s', QG.names[q], A.names[t], engine.last_error())
+    if paths:
+        alns, first, blk = alns
+        first, blk = dist.allgather_paths(first, blk)
     alns = dist.allgather_records(alns)
-    blocks, kept = formats.tab_blocks(alns, A.names, QG.names, min_len, min_idt)
-    return blocks, int(alns.size), kept
+    if not paths:
+        blocks, kept = formats.tab_blocks(alns, A.names, QG.names, min_len, min_idt)
+        return blocks, int(alns.size), kept
+    rows = []
+    blocks, kept = formats.tab_blocks(alns, A.names, QG.names, min_len, min_idt, rows=rows)
+    f2, b2 = formats.select_paths(first, blk, rows[0])
+    paf = formats.paf_lines(alns[rows[0]], f2, b2, A.names, A.lengths, QG.names, QG.lengths)
+    paf_blocks, at = {}, 0
+    for pr in sorted(blocks):   # tab_blocks makes its blocks in (tid, qid) order
+        paf_blocks[pr] = paf[at:at + len(blocks[pr])]
+        at += len(blocks[pr])
+    return blocks, int(alns.size), kept, paf_blocks
+
+
+def write_paf(path, pairs, paf_blocks, splitSelf=False):
+    """--paf: the PAF row of every row of the TAB, in the TAB's order (write_tab); with --strictSelf the rows of the
+    same-scaffold TAB follow those of the main one.  No header: PAF has none."""
+    with open(path, 'w') as f:
+        for intra in ((False, True) if splitSelf else (None,)):
+            for pr in pairs:
+                if intra is not None and (pr[0] == pr[1]) != intra:
+                    continue
+                for line in paf_blocks.get(pr, ()):
+                    f.write(line + '\n')
 
 
 def write_tab(path, pairs, blocks, select=None):
@@ -117,8 +153,9 @@ def collapse_to_gff(tab_path, names, lengths, min_cov, min_len, source, label, p
 
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
-                 B=None, anchor_rule='box', bound_extensions=False):
-    """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  anchor_rule: the gapped stage's skip rule, 'box' or
+                 B=None, anchor_rule='box', bound_extensions=False, paf=None):
+    """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
+    CIGARs to this file (--paf; nothing when the TAB is recycled).  anchor_rule: the gapped stage's skip rule, 'box' or
     'path' (or its _ffi.ANCHOR_* number; mimeo_hip.h MIMEO_ANCHOR_*).  bound_extensions: bound every gapped extension by
     the earlier alignments of its pair and strand (mimeo_params.bound_extensions); ValueError without the path rule."""
     dist = dist or Dist()
@@ -126,7 +163,9 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     kept = None
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
-        blocks, _, kept = align_blocks(A, B, pairs, params, minLen, minIdt, dist)
+        blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None)
+        if paf is not None and dist.rank == 0:
+            write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None)
         if len(set(pairs)) != len(pairs):
             kept = None   # a pair listed twice is written twice (the reference would run it twice): read the file back instead
         if dist.rank == 0:
@@ -159,15 +198,17 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
 
 
 def map_hits(A, B, pairs, outtab, minIdt=95, minLen=100, hspthresh=3000, reuseTab=False, dist=None, anchor_rule='box',
-             bound_extensions=False):
-    """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse.  anchor_rule and bound_extensions
-    as self_repeats."""
+             bound_extensions=False, paf=None):
+    """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse.  anchor_rule, bound_extensions and
+    paf as self_repeats."""
     dist = dist or Dist()
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
-        blocks, _, _ = align_blocks(A, B, pairs, params, minLen, minIdt, dist)
+        blocks, _, _, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None)
         if dist.rank == 0:
             write_tab(outtab, pairs, blocks)
+            if paf is not None:
+                write_paf(paf, pairs, more[0])
 
 
 def trf_filter(rows, A, prefix=None, tmatch=2, tmismatch=7, tminscore=50, tmaxperiod=50, maxtandem=40, tdelta=7):
