@@ -326,6 +326,46 @@ int mimeo_align_units_paths(const mimeo_genome *A, const mimeo_genome *B, const 
                             uint64_t **path_first, mimeo_path_block **blocks, uint64_t *nblocks);
 
 /*
+ * Column statistics of alignment paths (kernel K9): what the aligned columns of each alignment ARE, where the path only says
+ * where they lie.  Replaces nothing in the reference, which keeps lastz's identity column and no alignment; it is what a
+ * substitution divergence (Kimura's two-parameter distance needs transitions and transversions apart) and the NM / de tags
+ * of a PAF row are computed from.  The sequences are read from the device-resident genomes: no base text crosses the ABI.
+ *
+ * aln[0 .. n) are records as the align entry points return them, of target scaffolds of T and query scaffolds of Q (NULL: of
+ * T, a self job); the path of record i is blocks[path_first[i] .. path_first[i + 1]) in the coordinates of mimeo_path_block
+ * above (t on the target plus strand, q on the strand that was aligned); path_first has n + 1 entries.  Of a record only tid,
+ * qid and qstrand are read.  out[i] receives, for the columns of record i's blocks with target base x and query base y,
+ *   ambiguous      x or y is not one of ACGT
+ *   matches        x == y
+ *   transitions    A<->G or C<->T
+ *   transversions  every other pair of different bases
+ * and from the jumps between consecutive blocks the gaps, with the meaning of I and D in a CIGAR whose reference is the
+ * target: ins_runs / ins_bases are the runs and the bases of query sequence absent from the target, del_runs / del_bases
+ * those of target sequence absent from the query (both jump: one run of each).
+ *
+ * What a caller may rely on, for paths that mimeo_align_units_paths returned with these records:
+ *   - matches == id_n, and matches + transitions + transversions + ambiguous == id_d;
+ *   - del_bases == tend - tstart - id_d and ins_bases == qend - qstart - id_d;
+ *   - the counts are exact integers: they depend on nothing but the sequences and the blocks.
+ * Any path is accepted that keeps the contract of mimeo_path_block; everything is checked before the device sees it, and a
+ * violation is MIMEO_ERR_ARG with a message naming the record and the block: path_first[0] == 0, path_first non-decreasing,
+ * path_first[n] == nblocks; tid / qid inside their genomes, qstrand 0 or 1; len >= 1, t + len and q + len inside their
+ * scaffolds; the blocks of an alignment increasing and non-overlapping.  An alignment without blocks counts nothing.
+ * n == 0 returns MIMEO_OK at once.  Records and blocks go to the device in slices of bounded size, so a job of any size runs
+ * in the memory that is free next to the genomes.
+ *
+ * A new symbol beside the old ones, like mimeo_align_units_paths: MIMEO_ABI_VERSION stays 3; a host that needs it checks for
+ * the symbol.
+ */
+typedef struct mimeo_column_stats {
+    uint32_t matches, transitions, transversions, ambiguous;   /* their sum is id_d */
+    uint32_t ins_runs, ins_bases, del_runs, del_bases;         /* I / D of the CIGAR: runs and bases */
+} mimeo_column_stats;                                          /* 32 bytes */
+int mimeo_path_stats(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, const mimeo_alignment *aln, uint64_t n,
+                     const uint64_t *path_first, const mimeo_path_block *blocks, uint64_t nblocks,
+                     mimeo_column_stats *out /* caller's, n entries */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  mimeo_last_error() describes the last one.

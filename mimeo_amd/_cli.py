@@ -49,12 +49,19 @@ def add_common(parser, prog, gff_default, label, prefix, with_b):
                         help='Also write the rows of the alignment file as PAF with their alignments (cg:Z: CIGAR of M/I/D, AS:i: score) '
                              'to FILE, in the same order. Off by default: without it no path is computed. Ignored with --recycle '
                              'when the alignment file exists.')
+    parser.add_argument('--divergence', action='store_true', default=False,
+                        help='With --paf: every PAF row also carries NM:i: (edit distance), de:f: (gap-compressed divergence), ts:i: / '
+                             'tv:i: (transitions, transversions) and kd:f: (Kimura two-parameter distance; left out where undefined), '
+                             'counted on the GPU from the alignment\'s columns. An error without --paf. Ignored with --recycle when the '
+                             'alignment file exists.')
 
 
 def check_common(parser, args):
     """cross-flag rules of add_common (parser.error exits with status 2)"""
     if args.boundExtensions and args.anchorRule != 'path':
         parser.error('--boundExtensions needs --anchorRule path')
+    if args.divergence and not args.paf:
+        parser.error('--divergence needs --paf')
     return args
 
 

@@ -18,7 +18,7 @@ SYMBOLS = [
     'mimeo_genome_length', 'mimeo_seed_hits', 'mimeo_ungapped_hsps', 'mimeo_align_pair', 'mimeo_align_pairs',
     'mimeo_coverage_collapse', 'mimeo_tandem_masked', 'mimeo_genome_load_fasta', 'mimeo_genome_name',
     'mimeo_genome_keep_indexes', 'mimeo_genome_drop_indexes', 'mimeo_genome_build_indexes', 'mimeo_coverage_bedgraph',
-    'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths',
+    'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths', 'mimeo_path_stats',
 ]
 
 
@@ -66,6 +66,8 @@ ALIGNMENT = np.dtype([('tid', '<u4'), ('qid', '<u4'), ('tstart', '<u4'), ('tend'
                       ('reserved', '<u4')])
 INTERVAL = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4')])
 PATH_BLOCK = np.dtype([('t', '<u4'), ('q', '<u4'), ('len', '<u4')])   # mimeo_path_block
+COLUMN_STATS = np.dtype([(n, '<u4') for n in ('matches', 'transitions', 'transversions', 'ambiguous', 'ins_runs', 'ins_bases', 'del_runs',
+                                               'del_bases')])   # mimeo_column_stats, 32 bytes
 DEPTH_RUN = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4'), ('depth', '<u4')])
 
 _lib = None
@@ -111,6 +113,8 @@ def load():
     if hasattr(lib, 'mimeo_align_units_paths'):
         lib.mimeo_align_units_paths.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(Params), C.POINTER(vp), C.POINTER(u64),
                                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    if hasattr(lib, 'mimeo_path_stats'):
+        lib.mimeo_path_stats.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

@@ -375,6 +375,15 @@ int mimeo_align_units_paths(const mimeo_genome *A, const mimeo_genome *B, const 
     return align_units_impl(A, B == A ? nullptr : B, pair_t, pair_q, pair_strand, npairs, p, out, nout, path_first, blocks, nblocks);
 }
 
+int mimeo_path_stats(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first,
+                     const mimeo_path_block *blocks, uint64_t nblocks, mimeo_column_stats *out) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!n) return MIMEO_OK;
+    if (!T || !aln || !path_first || !out || (nblocks && !blocks)) { set_error("mimeo_path_stats: null argument"); return MIMEO_ERR_ARG; }
+    return path_stats_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, out);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

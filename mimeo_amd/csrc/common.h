@@ -334,4 +334,8 @@ int build_kept_indexes(mimeo_genome *g, const uint32_t *scaf, uint64_t n);  // p
 int tandem_masked_device(const mimeo_genome *A, const mimeo_interval *h_iv, uint64_t n, int match, int mismatch, int delta,
                          int minscore, int maxperiod, uint32_t *h_masked);
 
+// K9: column statistics of alignment paths (k9_path_stats.hip); host in, host out.  Q is never null here.
+int path_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
+                      const mimeo_path_block *blocks, uint64_t nblocks, mimeo_column_stats *out);
+
 }  // namespace mimeo

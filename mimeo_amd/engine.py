@@ -180,6 +180,24 @@ def align_units(A, B, units, params=None, paths=False):
     return _ffi.take(ptr, n, _ffi.ALIGNMENT)
 
 
+def path_stats(A, B, records, first, blocks):
+    """Column statistics of alignment paths (mimeo_path_stats, kernel K9): one _ffi.COLUMN_STATS row per record — matches,
+    transitions, transversions and ambiguous columns of its blocks blocks[first[i]:first[i + 1]], insertion / deletion runs and
+    bases between them.  records / first / blocks as align_pairs(..., paths=True) returns them (or any selection of them:
+    formats.select_paths); B = None: the queries are scaffolds of A.  A path that breaks the contract of mimeo_path_block is a
+    RuntimeError naming the record, raised before anything runs on the device."""
+    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
+    if first.size != recs.size + 1:
+        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
+    out = np.zeros(recs.size, dtype=_ffi.COLUMN_STATS)
+    if recs.size:
+        _ffi.check(_ffi.load().mimeo_path_stats(A._h, B._h if B is not None else None, recs.ctypes.data, recs.size, first.ctypes.data,
+                                                blk.ctypes.data if blk.size else None, blk.size, out.ctypes.data))
+    return out
+
+
 def failed_pairs():
     """Pairs of the last align_pairs / align_units call that hit a documented limit and were left out (the reference's script
     loses only the failing lastz run's rows: utils.py:125-128): [(index into the call's pair list, error code)]."""

@@ -3,6 +3,7 @@ lastz and bedtools calls.  Every function cites the reference command text it re
 relative to /root/reference/src/mimeo); the engine (HIP) supplies the numbers, these functions
 supply the bytes.
 """
+import math
 import os
 import re
 
@@ -155,6 +156,29 @@ def cigar(blocks):
     return ''.join(ops)
 
 
+def divergence_tags(s):
+    """The divergence tags of one PAF row from its column statistics `s` (one row of engine.path_stats, or a mapping with the
+    fields of _ffi.COLUMN_STATS), tab-separated.  With mism = transitions + transversions + ambiguous:
+      NM:i:  mism + inserted + deleted bases (the edit distance of the alignment)
+      de:f:  (mism + gap runs) / (matches + mism + gap runs): minimap2's gap-compressed divergence
+      ts:i: / tv:i:  transitions and transversions
+      kd:f:  Kimura's two-parameter distance -1/2 ln((1 - 2P - Q) sqrt(1 - 2Q)), P = ts / n, Q = tv / n over the
+             n = matches + ts + tv unambiguous columns; left out where it is undefined (n == 0 or a factor <= 0: saturated)
+    The counts are the engine's exact integers; the floating-point arithmetic is the host's."""
+    m, ts, tv, amb = int(s['matches']), int(s['transitions']), int(s['transversions']), int(s['ambiguous'])
+    runs = int(s['ins_runs']) + int(s['del_runs'])
+    mism = ts + tv + amb
+    den = m + mism + runs
+    tags = ['NM:i:%d' % (mism + int(s['ins_bases']) + int(s['del_bases'])), 'de:f:%.4f' % ((mism + runs) / den if den else 0.0),
+            'ts:i:%d' % ts, 'tv:i:%d' % tv]
+    n = m + ts + tv
+    if n:
+        a, b = 1.0 - 2.0 * ts / n - tv / n, 1.0 - 2.0 * tv / n
+        if a > 0.0 and b > 0.0:
+            tags.append('kd:f:%.4f' % (0.0 - 0.5 * math.log(a * math.sqrt(b))))   # 0.0 - x: no '-0.0000' for identical sequences
+    return '\t'.join(tags)
+
+
 def select_paths(first, blocks, rows):
     """(first, blocks) of the alignments `rows` (indexes), in that order"""
     first = np.asarray(first, dtype=np.int64)
@@ -166,21 +190,23 @@ def select_paths(first, blocks, rows):
     return out, blocks[take]
 
 
-def paf_lines(records, first, blocks, tnames, tlens, qnames, qlens):
+def paf_lines(records, first, blocks, tnames, tlens, qnames, qlens, stats=None):
     """One PAF row per record: query name, length, start, end (0-based half-open, query plus strand), strand, target name,
     length, start, end, residue matches (id_n), alignment length (id_d + gap bases), 255 (no mapping quality), then
     AS:i:<score> and cg:Z:<cigar>.  The path of record i is blocks[first[i]:first[i + 1]] (mimeo_hip.h,
     mimeo_align_units_paths): t on the target plus strand, q on the aligned strand, so the CIGAR of a '-' row runs along the
-    target forward and the reverse-complemented query — PAF's own meaning."""
+    target forward and the reverse-complemented query — PAF's own meaning.  stats (one row of engine.path_stats per record;
+    --divergence): the tags of divergence_tags between AS:i: and cg:Z:."""
     lines = []
     for i in range(len(records)):
         r = records[i]
         b = blocks[int(first[i]):int(first[i + 1])]
         gaps = (int(r['tend']) - int(r['tstart']) - int(r['id_d'])) + (int(r['qend']) - int(r['qstart']) - int(r['id_d']))
         t, q = int(r['tid']), int(r['qid'])
-        lines.append('%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tcg:Z:%s' % (
+        lines.append('%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\t%scg:Z:%s' % (
             qnames[q], int(qlens[q]), int(r['qstart']), int(r['qend']), '-' if int(r['qstrand']) else '+', tnames[t], int(tlens[t]),
-            int(r['tstart']), int(r['tend']), int(r['id_n']), int(r['id_d']) + gaps, int(r['score']), cigar(b)))
+            int(r['tstart']), int(r['tend']), int(r['id_n']), int(r['id_d']) + gaps, int(r['score']),
+            divergence_tags(stats[i]) + '\t' if stats is not None else '', cigar(b)))
     return lines
 
 

@@ -33,7 +33,7 @@ def main(argv=None):
     workflow.self_repeats(A, pairs, outtab, gffout, minIdt=args.minIdt, minLen=args.minLen, hspthresh=3000,
                           minCov=args.minCov, reuseTab=args.recycle, label=args.label, prefix=args.prefix, dist=dist,
                           source='mimeo', B=B, anchor_rule=args.anchorRule,
-                          bound_extensions=args.boundExtensions, paf=args.paf)
+                          bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

@@ -34,7 +34,7 @@ def main(argv=None):
     workflow.self_repeats(A, pairs, outtab, gffout, minIdt=args.minIdt, minLen=args.minLen, hspthresh=args.hspthresh,
                           minCov=args.minCov, intraCov=args.intraCov, splitSelf=args.strictSelf, reuseTab=args.recycle,
                           label=args.label, prefix=args.prefix, dist=dist,
-                          anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf)
+                          anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

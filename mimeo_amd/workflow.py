@@ -45,7 +45,7 @@ PACK_MEMBER_BP = 6 << 20   # the engine packs scaffolds of up to this size into 
 PACK_MIN = 8               # ... this many of them (mimeo_hip.h, mimeo_align_pairs)
 
 
-def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False):
+def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, divergence=False):
     """Align every pair (sharded over ranks when dist.world > 1) and return {(t, q): [TAB lines]} on every rank, the raw
     record count and the (n, 4) array of (tid, qid, start1, end1) of the rows kept — what the BED projection of the TAB reads
     back (wrappers.py:1120-1128).
@@ -58,7 +58,9 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False):
 
     paths=True (--paf): the engine also returns every alignment's path, the block counts and the blocks travel through the
     same all-gatherv as the records, and a fourth value comes back: {(t, q): [PAF lines]}, the rows of the TAB blocks in
-    their order."""
+    their order.  divergence=True (--divergence, with paths): rank 0, which writes the file, also asks the engine for the column
+    statistics of the rows that are written (engine.path_stats on the kept rows only: every rank holds the genomes and the
+    gathered paths, so no collective is added) and its PAF lines carry the tags of formats.divergence_tags."""
     dist = dist or Dist()
     none = (np.zeros(0, dtype=engine._ffi.ALIGNMENT), np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=engine._ffi.PATH_BLOCK))
     first = blk = None
@@ -102,7 +104,8 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False):
     rows = []
     blocks, kept = formats.tab_blocks(alns, A.names, QG.names, min_len, min_idt, rows=rows)
     f2, b2 = formats.select_paths(first, blk, rows[0])
-    paf = formats.paf_lines(alns[rows[0]], f2, b2, A.names, A.lengths, QG.names, QG.lengths)
+    stats = engine.path_stats(A, B, alns[rows[0]], f2, b2) if divergence and dist.rank == 0 else None
+    paf = formats.paf_lines(alns[rows[0]], f2, b2, A.names, A.lengths, QG.names, QG.lengths, stats=stats)
     paf_blocks, at = {}, 0
     for pr in sorted(blocks):   # tab_blocks makes its blocks in (tid, qid) order
         paf_blocks[pr] = paf[at:at + len(blocks[pr])]
@@ -153,9 +156,10 @@ def collapse_to_gff(tab_path, names, lengths, min_cov, min_len, source, label, p
 
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
-                 B=None, anchor_rule='box', bound_extensions=False, paf=None):
+                 B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
-    CIGARs to this file (--paf; nothing when the TAB is recycled).  anchor_rule: the gapped stage's skip rule, 'box' or
+    CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
+    divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
     'path' (or its _ffi.ANCHOR_* number; mimeo_hip.h MIMEO_ANCHOR_*).  bound_extensions: bound every gapped extension by
     the earlier alignments of its pair and strand (mimeo_params.bound_extensions); ValueError without the path rule."""
     dist = dist or Dist()
@@ -163,7 +167,8 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     kept = None
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
-        blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None)
+        blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None,
+                                               divergence=divergence and paf is not None)
         if paf is not None and dist.rank == 0:
             write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None)
         if len(set(pairs)) != len(pairs):
@@ -198,13 +203,14 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
 
 
 def map_hits(A, B, pairs, outtab, minIdt=95, minLen=100, hspthresh=3000, reuseTab=False, dist=None, anchor_rule='box',
-             bound_extensions=False, paf=None):
-    """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse.  anchor_rule, bound_extensions and
-    paf as self_repeats."""
+             bound_extensions=False, paf=None, divergence=False):
+    """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse.  anchor_rule, bound_extensions,
+    paf and divergence as self_repeats."""
     dist = dist or Dist()
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
-        blocks, _, _, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None)
+        blocks, _, _, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None,
+                                            divergence=divergence and paf is not None)
         if dist.rank == 0:
             write_tab(outtab, pairs, blocks)
             if paf is not None:
