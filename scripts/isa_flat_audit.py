@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """flat_* / global_* / scratch_* accesses per kernel in the gfx950 assembly of the extension, chain and gapped kernels.
 
-    python scripts/isa_flat_audit.py [file.hip ...]      (default: the four files below; needs hipcc, no GPU)
+    python scripts/isa_flat_audit.py [file.hip ...]      (default: the files below; needs hipcc, no GPU)
 
 A pointer that a kernel loads from a device table (the StrandView / IndexView members of UnitDesc, FusedUnit, Group) is a
 generic pointer to the compiler, and every access through it is a flat_* instruction: it may address LDS, so it is not
@@ -20,7 +20,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'mimeo_amd', 'csrc')
-FILES = ['k34_fused.hip', 'k4_extend.hip', 'k5_chain.hip', 'k6_gapped.hip', 'k9_path_stats.hip']
+FILES = ['k34_fused.hip', 'k4_extend.hip', 'k5_chain.hip', 'k6_gapped.hip', 'k6_dp.hip', 'k6_trace.hip', 'k6_paths.hip', 'k9_path_stats.hip']
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-w', '-S', '--cuda-device-only']
 # kernels (name without template arguments) that may keep flat_* accesses, each with its reason
 ALLOW = {

@@ -144,8 +144,8 @@ def test_flanked_genome_all_layouts(eng, monkeypatch, capfd):
 
 def test_long_half_under_a_low_score_cap(eng, monkeypatch):
     """The 300 kb extension under a low score cap: too many rows for the register kernel, so the bounded k6_dp_any runs it
-    and rebases its cells, and the bounded trace re-run ends on the same cell.  (Bands beyond the register kernel: the
-    y-drop 90000 case of bounded_oracle.flanked_cases.)"""
+    and rebases its cells, and the bounded trace re-run, which takes the same cap and rebases as it goes, ends on the same
+    cell.  (Bands beyond the register kernel: the y-drop 90000 case of bounded_oracle.flanked_cases.)"""
     rng = np.random.default_rng(123)
     acgt = np.frombuffer(b'ACGT', dtype=np.uint8)
     core = rng.integers(0, 4, 300_000)

@@ -129,7 +129,8 @@ def test_path_rule_all_layouts(eng, monkeypatch, capfd):
 
 def test_path_rule_wide_bands_long_halves_and_self(eng, monkeypatch):
     """Bands beyond 2048 columns (k6_dp_any; the trace keeps its rows in the pool), the 300 kb extension under a low score cap
-    (k6_dp_any rebases its cells), and the (A, A) self pair whose identical-suffix shortcut has the diagonal as its path."""
+    (k6_dp_any rebases its cells, and so does k6_trace: the cap reaches the trace, whose re-run shares the band DP and its rebase),
+    and the (A, A) self pair whose identical-suffix shortcut has the diagonal as its path."""
     names, seqs = synth_genome(97, 120_000, 2, repeat_frac=0.2, families=2, cons_len=(800, 2000), max_div=0.1)
     tn, tseqs = tandem_genome(11, 2, 200_000)
     rng = np.random.default_rng(123)
