@@ -464,6 +464,12 @@ static int round_stats(uint32_t n, uint64_t nhsps, bool bounded, unsigned long l
         for (int b = 14; b < 34; b++) fprintf(stderr, " %llu", fine[b]);
         fprintf(stderr, "\n");
     }
+    // a round of a few jobs: what each half came back with, in job order — the band width tells the kernel that finished it (a
+    // multiple of 14 up to 882: k6_dp1; of 32 up to 2016: k6_dp_wide; the exact width: k6_dp_any)
+    if (n <= 8)
+        for (size_t k = 0; k < hr.size(); k++)
+            fprintf(stderr, "  [k6] job %zu: dir %d rows %u maxcols %u i %u j %u rebased %d\n", k, hj[k].dir, hr[k].rows, hr[k].maxcols, hr[k].i, hr[k].j,
+                    (hr[k].base_lo | hr[k].base_hi) ? 1 : 0);
     int shown = 0;
     for (auto &r : hr)
         if (!r.rows && shown < 8) { fprintf(stderr, "  [k6] zero-row job: score %d i %u j %u nm %u nx %u ovf %u\n", r.score, r.i, r.j, r.nm, r.nx, r.overflow); shown++; }
