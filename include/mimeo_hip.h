@@ -366,6 +366,52 @@ int mimeo_path_stats(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */,
                      mimeo_column_stats *out /* caller's, n entries */);
 
 /*
+ * Column statistics of alignment paths clipped to target windows and accumulated into groups (kernel K10): what ties a
+ * divergence to a REGION of the target — a repeat of `mimeo self`, a candidate of `mimeo x` — where mimeo_path_stats counts
+ * whole alignments.  An alignment routinely runs past a region's ends or across several regions, and the host holds no
+ * sequence text to clip with: the clipping is done on the device, from the device-resident genomes.
+ *
+ * T, Q, aln, n, path_first, blocks and nblocks are those of mimeo_path_stats.  An item asks for the path of record `aln`
+ * clipped to the window [w0, w1) on the plus strand of that record's target scaffold, added to group `group`.  With the
+ * path's blocks b_0 .. b_{m-1}, p_k = b_{k-1}.t + b_{k-1}.len the end of the block before b_k, dt_k = b_k.t - p_k and
+ * dq_k = b_k.q - (b_{k-1}.q + b_{k-1}.len):
+ *   columns     a column of b_k is counted iff its target base lies in [w0, w1); it is ambiguous, a match, a transition or a
+ *               transversion as for mimeo_path_stats: the N planes mask first;
+ *   del_bases   the overlap of [p_k, b_k.t) with [w0, w1);
+ *   del_runs    the run is counted iff dt_k > 0 and w0 <= p_k < w1: a run belongs to the window that holds its first base;
+ *   ins_runs, ins_bases   for dq_k > 0 the run and all dq_k bases are counted iff w0 <= p_k < w1: the insertion sits in front
+ *               of target base p_k (where both sequences jump, this is the I-then-D order of a CIGAR); an insertion is
+ *               never split.
+ * What follows, and what a caller may rely on:
+ *   - all eight fields are additive over any partition of a window;
+ *   - over a partition of [tstart, tend) they sum to what mimeo_path_stats returns for the alignment;
+ *   - a window that misses the alignment counts nothing, and so does an empty window (w0 == w1), which is legal;
+ *   - matches + transitions + transversions + ambiguous + del_bases is the length of the overlap of the window with
+ *     [tstart, tend).
+ * out[g], g < ngroups, is the sum over the items with group == g; a group without items is zero.  Items come in any order,
+ * and an alignment may appear in any number of them.  The counters are 64 bits: a region of megabases under hundreds of rows
+ * exceeds 2^32.  They are exact integers and depend on nothing but the sequences, the blocks and the items.
+ *
+ * Everything is checked before the device sees it; a violation is MIMEO_ERR_ARG with a message naming the item (or, for the
+ * paths, the record and the block): everything mimeo_path_stats checks; aln < n, group < ngroups, w0 <= w1, and w1 <= the
+ * length of the record's target scaffold.  nitems == 0 zeroes out[0 .. ngroups) and returns MIMEO_OK.  Records and blocks go
+ * to the device in the same bounded slices as for mimeo_path_stats, and only the slices that an item asks for.
+ *
+ * A new symbol beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs it checks for the symbol.
+ */
+typedef struct mimeo_window_item {
+    uint32_t aln, group, w0, w1;
+} mimeo_window_item;                                           /* 16 bytes */
+typedef struct mimeo_window_stats {
+    uint64_t matches, transitions, transversions, ambiguous;   /* columns whose target base lies in the window */
+    uint64_t ins_runs, ins_bases, del_runs, del_bases;         /* I / D of the CIGAR: runs and bases */
+} mimeo_window_stats;                                          /* 64 bytes */
+int mimeo_path_window_stats(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, const mimeo_alignment *aln, uint64_t n,
+                            const uint64_t *path_first, const mimeo_path_block *blocks, uint64_t nblocks,
+                            const mimeo_window_item *items, uint64_t nitems, uint64_t ngroups,
+                            mimeo_window_stats *out /* caller's, ngroups entries */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  mimeo_last_error() describes the last one.

@@ -56,6 +56,17 @@ def add_common(parser, prog, gff_default, label, prefix, with_b):
                              'alignment file exists.')
 
 
+def add_region_stats(parser):
+    """--regionStats of `mimeo self` and `mimeo x` (`mimeo map` has no regions)"""
+    parser.add_argument('--regionStats', type=str, default=None, metavar='FILE',
+                        help='Also write one line per feature of the GFF3 to FILE (tab-separated, with a header): the alignment rows that '
+                             'overlap the region, and the matches, transitions, transversions, ambiguous columns and insertion / deletion '
+                             'runs and bases of their alignments clipped to the region, counted on the GPU, with identity, gap-compressed '
+                             'divergence (de) and Kimura two-parameter distance (kd) over the region; "." where undefined. The trivial '
+                             'alignment of a scaffold with itself is left out. Needs neither --paf nor --divergence. Nothing is written '
+                             'with --recycle when the alignment file exists.')
+
+
 def check_common(parser, args):
     """cross-flag rules of add_common (parser.error exits with status 2)"""
     if args.boundExtensions and args.anchorRule != 'path':

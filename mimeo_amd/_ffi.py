@@ -19,6 +19,7 @@ SYMBOLS = [
     'mimeo_coverage_collapse', 'mimeo_tandem_masked', 'mimeo_genome_load_fasta', 'mimeo_genome_name',
     'mimeo_genome_keep_indexes', 'mimeo_genome_drop_indexes', 'mimeo_genome_build_indexes', 'mimeo_coverage_bedgraph',
     'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths', 'mimeo_path_stats',
+    'mimeo_path_window_stats',
 ]
 
 
@@ -68,6 +69,8 @@ INTERVAL = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4')])
 PATH_BLOCK = np.dtype([('t', '<u4'), ('q', '<u4'), ('len', '<u4')])   # mimeo_path_block
 COLUMN_STATS = np.dtype([(n, '<u4') for n in ('matches', 'transitions', 'transversions', 'ambiguous', 'ins_runs', 'ins_bases', 'del_runs',
                                                'del_bases')])   # mimeo_column_stats, 32 bytes
+WINDOW_ITEM = np.dtype([(n, '<u4') for n in ('aln', 'group', 'w0', 'w1')])   # mimeo_window_item, 16 bytes
+WINDOW_STATS = np.dtype([(n, '<u8') for n in COLUMN_STATS.names])   # mimeo_window_stats, 64 bytes: the fields of mimeo_column_stats in 64 bits
 DEPTH_RUN = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4'), ('depth', '<u4')])
 
 _lib = None
@@ -115,6 +118,8 @@ def load():
                                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     if hasattr(lib, 'mimeo_path_stats'):
         lib.mimeo_path_stats.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
+    if hasattr(lib, 'mimeo_path_window_stats'):
+        lib.mimeo_path_window_stats.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, u64, vp]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

@@ -384,6 +384,20 @@ int mimeo_path_stats(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_a
     return path_stats_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, out);
 }
 
+int mimeo_path_window_stats(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first,
+                            const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_window_item *items, uint64_t nitems, uint64_t ngroups,
+                            mimeo_window_stats *out) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (ngroups && !out) { set_error("mimeo_path_window_stats: null argument"); return MIMEO_ERR_ARG; }
+    if (!nitems) {
+        if (ngroups) memset(out, 0, ngroups * sizeof(mimeo_window_stats));
+        return MIMEO_OK;
+    }
+    if (!T || !items || (n && (!aln || !path_first)) || (nblocks && !blocks)) { set_error("mimeo_path_window_stats: null argument"); return MIMEO_ERR_ARG; }
+    return window_stats_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, items, nitems, ngroups, out);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

@@ -337,5 +337,10 @@ int tandem_masked_device(const mimeo_genome *A, const mimeo_interval *h_iv, uint
 // K9: column statistics of alignment paths (k9_path_stats.hip); host in, host out.  Q is never null here.
 int path_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
                       const mimeo_path_block *blocks, uint64_t nblocks, mimeo_column_stats *out);
+// K10: the same statistics clipped to target windows and summed into groups (k10_window_stats.hip); host in, host out.  Q is
+// never null here, and nitems > 0.
+int window_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
+                        const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_window_item *items, uint64_t nitems, uint64_t ngroups,
+                        mimeo_window_stats *out);
 
 }  // namespace mimeo

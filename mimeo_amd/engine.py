@@ -198,6 +198,32 @@ def path_stats(A, B, records, first, blocks):
     return out
 
 
+def window_stats(A, B, records, first, blocks, items, ngroups):
+    """Column statistics of alignment paths clipped to target windows and summed into groups (mimeo_path_window_stats, kernel
+    K10): an array of `ngroups` rows of _ffi.WINDOW_STATS.  records / first / blocks as for path_stats; items: _ffi.WINDOW_ITEM
+    rows (or an (n, 4) array) of (record number, group, w0, w1) — the columns of that record whose target base lies in
+    [w0, w1) of its target scaffold's plus strand, and the gaps that start there (include/mimeo_hip.h has the rules), are added
+    to the group.  Items come in any order; a group without items is zero.  A bad path or a bad item is a RuntimeError naming
+    it, raised before anything runs on the device."""
+    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
+    if first.size != recs.size + 1:
+        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
+    it = np.asarray(items)
+    if it.dtype != _ffi.WINDOW_ITEM:
+        a = np.asarray(it, dtype=np.uint32).reshape(-1, 4)
+        it = np.zeros(a.shape[0], dtype=_ffi.WINDOW_ITEM)
+        it['aln'], it['group'], it['w0'], it['w1'] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    it = np.ascontiguousarray(it)
+    out = np.zeros(int(ngroups), dtype=_ffi.WINDOW_STATS)
+    _ffi.check(_ffi.load().mimeo_path_window_stats(A._h, B._h if B is not None else None, recs.ctypes.data if recs.size else None, recs.size,
+                                                   first.ctypes.data, blk.ctypes.data if blk.size else None, blk.size,
+                                                   it.ctypes.data if it.size else None, it.size, int(ngroups),
+                                                   out.ctypes.data if out.size else None))
+    return out
+
+
 def failed_pairs():
     """Pairs of the last align_pairs / align_units call that hit a documented limit and were left out (the reference's script
     loses only the failing lastz run's rows: utils.py:125-128): [(index into the call's pair list, error code)]."""

@@ -165,18 +165,31 @@ def divergence_tags(s):
       kd:f:  Kimura's two-parameter distance -1/2 ln((1 - 2P - Q) sqrt(1 - 2Q)), P = ts / n, Q = tv / n over the
              n = matches + ts + tv unambiguous columns; left out where it is undefined (n == 0 or a factor <= 0: saturated)
     The counts are the engine's exact integers; the floating-point arithmetic is the host's."""
+    mism, runs, de, kd = divergence_values(s)
+    tags = ['NM:i:%d' % (mism + int(s['ins_bases']) + int(s['del_bases'])), 'de:f:%.4f' % (de if de is not None else 0.0),
+            'ts:i:%d' % int(s['transitions']), 'tv:i:%d' % int(s['transversions'])]
+    if kd is not None:
+        tags.append('kd:f:%.4f' % kd)
+    return '\t'.join(tags)
+
+
+def divergence_values(s):
+    """The floating-point arithmetic of divergence_tags and region_stat_lines on one row of column statistics (32- or 64-bit
+    fields): (mism, gap runs, de, kd) with mism = transitions + transversions + ambiguous; de = (mism + runs) / (matches + mism +
+    runs), None where there is no column and no run; kd = Kimura's two-parameter distance, None where it is undefined (no
+    unambiguous column, or a factor <= 0: saturated)."""
     m, ts, tv, amb = int(s['matches']), int(s['transitions']), int(s['transversions']), int(s['ambiguous'])
     runs = int(s['ins_runs']) + int(s['del_runs'])
     mism = ts + tv + amb
     den = m + mism + runs
-    tags = ['NM:i:%d' % (mism + int(s['ins_bases']) + int(s['del_bases'])), 'de:f:%.4f' % ((mism + runs) / den if den else 0.0),
-            'ts:i:%d' % ts, 'tv:i:%d' % tv]
+    de = (mism + runs) / den if den else None
+    kd = None
     n = m + ts + tv
     if n:
         a, b = 1.0 - 2.0 * ts / n - tv / n, 1.0 - 2.0 * tv / n
         if a > 0.0 and b > 0.0:
-            tags.append('kd:f:%.4f' % (0.0 - 0.5 * math.log(a * math.sqrt(b))))   # 0.0 - x: no '-0.0000' for identical sequences
-    return '\t'.join(tags)
+            kd = 0.0 - 0.5 * math.log(a * math.sqrt(b))   # 0.0 - x: no '-0.0000' for identical sequences
+    return mism, runs, de, kd
 
 
 def select_paths(first, blocks, rows):
@@ -260,6 +273,77 @@ def gff_repeat_lines(regions, names_sorted, source, label, prefix):
     for i, r in enumerate(regions, 1):
         lines.append('\t'.join([names_sorted[int(r['chrom'])], source, label, str(int(r['start'])), str(int(r['end'])),
                                 '.', '+', '.', 'ID=%s_%05d' % (prefix, i)]))
+    return lines
+
+
+WINDOW_ITEM = np.dtype([(n, '<u4') for n in ('aln', 'group', 'w0', 'w1')])   # _ffi.WINDOW_ITEM (this module does not load the library)
+REGION_STATS_FIELDS = ('matches', 'transitions', 'transversions', 'ambiguous', 'ins_runs', 'ins_bases', 'del_runs', 'del_bases')
+REGION_STATS_HEADER = '\t'.join(('#ID', 'seqid', 'start', 'end', 'rows', 'covered', 'columns') + REGION_STATS_FIELDS + ('identity', 'de', 'kd'))
+
+
+def region_items(records, regions, chrom_of_tid, first=None, blocks=None, self_job=False):
+    """The join of alignments and repeat regions for engine.window_stats: for every record and every region of its target
+    scaffold with [tstart, tend) and [start, end) overlapping, one item (record number, region number, max(start, tstart),
+    min(end, tend)).  records: engine records; regions: the _ffi.INTERVAL rows engine.coverage_collapse returns — sorted by
+    (chrom, start) and disjoint; chrom_of_tid[tid]: the region chromosome number of target scaffold tid (the collapse numbers
+    the scaffolds in sorted-name order, the engine in FASTA order).
+
+    A region is the half-open interval [start, end) the collapse computed, the numbers printed in its GFF3 row; the record's
+    side is its true 0-based tstart — NOT the origin-one start1 that the BED projection feeds to the collapse un-shifted
+    (bed_intervals): the statistics are those of the alignment's columns that lie on the region's bases.
+
+    self_job (with first, blocks: the records' paths): the trivial self rows are left out — same scaffold, plus strand, and a
+    path of exactly one block with t == q, a sequence against itself.  They are all matches and would only dilute every region.
+    Returns (items, rows): WINDOW_ITEM rows ordered by record, then region, and the number of items of every region."""
+    nreg = len(regions)
+    none = (np.zeros(0, dtype=WINDOW_ITEM), np.zeros(nreg, dtype=np.int64))
+    if len(records) == 0 or nreg == 0:
+        return none
+    rec = np.arange(len(records), dtype=np.int64)
+    if self_job:
+        if first is None or blocks is None:
+            raise ValueError('self_job needs the paths (first, blocks) to tell the trivial self rows')
+        first = np.asarray(first, dtype=np.int64)
+        one = first[1:] - first[:-1] == 1
+        b = blocks[first[:-1][one]]
+        on_diagonal = np.zeros(len(records), dtype=bool)
+        on_diagonal[one] = b['t'] == b['q']
+        trivial = on_diagonal & (records['tid'] == records['qid']) & (records['qstrand'] == 0)
+        rec = rec[~trivial]
+    chrom = np.asarray(chrom_of_tid, dtype=np.int64)[records['tid'][rec].astype(np.int64)]
+    ts, te = records['tstart'][rec].astype(np.int64), records['tend'][rec].astype(np.int64)
+    rc, rs, re_ = regions['chrom'].astype(np.int64), regions['start'].astype(np.int64), regions['end'].astype(np.int64)
+    # one key orders (chrom, position); the regions are disjoint, so their ends are sorted like their starts
+    lo = np.searchsorted(rc << 32 | re_, chrom << 32 | ts, side='right')   # the first region that ends behind tstart
+    hi = np.searchsorted(rc << 32 | rs, chrom << 32 | te, side='left')     # one past the last region that starts in front of tend
+    cnt = np.maximum(hi - lo, 0)
+    total = int(cnt.sum())
+    if total == 0:
+        return none
+    src = np.repeat(np.arange(rec.size), cnt)
+    grp = np.repeat(lo - (np.cumsum(cnt) - cnt), cnt) + np.arange(total)
+    w0, w1 = np.maximum(rs[grp], ts[src]), np.minimum(re_[grp], te[src])
+    keep = w0 < w1   # a record without a base has no overlap
+    items = np.zeros(int(keep.sum()), dtype=WINDOW_ITEM)
+    items['aln'], items['group'], items['w0'], items['w1'] = rec[src][keep], grp[keep], w0[keep], w1[keep]
+    return items, np.bincount(grp[keep], minlength=nreg).astype(np.int64)
+
+
+def region_stat_lines(regions, names_sorted, prefix, stats, rows, header=True):
+    """--regionStats: REGION_STATS_HEADER (header=True), then one tab-separated line per region.  ID, seqid, start and end are
+    those of the region's GFF3 row (gff_repeat_lines); rows: the alignments that overlap the region (region_items); stats: its
+    row of engine.window_stats; columns = matches + transitions + transversions + ambiguous; covered = columns + del_bases (the
+    region's bases under an alignment, each counted once per alignment); identity = matches / columns; de and kd as in
+    divergence_tags, over the region's sums.  A quantity that is undefined prints as '.'."""
+    lines = [REGION_STATS_HEADER] if header else []
+    for i, r in enumerate(regions, 1):
+        s = stats[i - 1]
+        c = [int(s[f]) for f in REGION_STATS_FIELDS]
+        columns = c[0] + c[1] + c[2] + c[3]
+        _, _, de, kd = divergence_values(s)
+        lines.append('\t'.join([('%s_%05d' % (prefix, i)), names_sorted[int(r['chrom'])], str(int(r['start'])), str(int(r['end'])), str(int(rows[i - 1])),
+                                str(columns + c[7]), str(columns)] + [str(v) for v in c] +
+                               ['%.4f' % (c[0] / columns) if columns else '.', '%.4f' % de if de is not None else '.', '%.4f' % kd if kd is not None else '.']))
     return lines
 
 

@@ -14,6 +14,7 @@ def mainArgs(argv=None):
         prog='mimeo-x')
     _cli.add_common(parser, 'mimeo-x', 'mimeo_B_in_A.gff3', 'B_Repeat', 'B_Repeat', with_b=True)
     parser.add_argument('--bedtools', type=str, default='bedtools', help='Accepted for compatibility; bedtools is not used.')
+    _cli.add_region_stats(parser)
     parser.add_argument('--minCov', type=int, default=5, help='Minimum depth of B-genome hits to report feature in A-genome.')
     return _cli.check_common(parser, parser.parse_args(argv))
 
@@ -33,7 +34,8 @@ def main(argv=None):
     workflow.self_repeats(A, pairs, outtab, gffout, minIdt=args.minIdt, minLen=args.minLen, hspthresh=3000,
                           minCov=args.minCov, reuseTab=args.recycle, label=args.label, prefix=args.prefix, dist=dist,
                           source='mimeo', B=B, anchor_rule=args.anchorRule,
-                          bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence)
+                          bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence,
+                          region_stats=args.regionStats)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

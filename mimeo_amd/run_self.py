@@ -12,6 +12,7 @@ def mainArgs(argv=None):
                     'segments above an coverage threshold.', prog='mimeo-self')
     _cli.add_common(parser, 'mimeo-self', 'mimeo-self_repeats.gff3', 'Self_Repeat', 'Self_Repeat', with_b=False)
     parser.add_argument('--bedtools', type=str, default='bedtools', help='Accepted for compatibility; bedtools is not used.')
+    _cli.add_region_stats(parser)
     parser.add_argument('--minCov', type=int, default=3, help='Minimum depth of aligned segments to report repeat feature.')
     parser.add_argument('--intraCov', type=int, default=5,
                         help='Minimum depth of aligned segments from same scaffold to report feature. Used if "--strictSelf" mode is selected.')
@@ -34,7 +35,8 @@ def main(argv=None):
     workflow.self_repeats(A, pairs, outtab, gffout, minIdt=args.minIdt, minLen=args.minLen, hspthresh=args.hspthresh,
                           minCov=args.minCov, intraCov=args.intraCov, splitSelf=args.strictSelf, reuseTab=args.recycle,
                           label=args.label, prefix=args.prefix, dist=dist,
-                          anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence)
+                          anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence,
+                          region_stats=args.regionStats)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

@@ -45,7 +45,7 @@ PACK_MEMBER_BP = 6 << 20   # the engine packs scaffolds of up to this size into 
 PACK_MIN = 8               # ... this many of them (mimeo_hip.h, mimeo_align_pairs)
 
 
-def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, divergence=False):
+def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, divergence=False, paf_rows=True):
     """Align every pair (sharded over ranks when dist.world > 1) and return {(t, q): [TAB lines]} on every rank, the raw
     record count and the (n, 4) array of (tid, qid, start1, end1) of the rows kept — what the BED projection of the TAB reads
     back (wrappers.py:1120-1128).
@@ -60,7 +60,9 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, 
     same all-gatherv as the records, and a fourth value comes back: {(t, q): [PAF lines]}, the rows of the TAB blocks in
     their order.  divergence=True (--divergence, with paths): rank 0, which writes the file, also asks the engine for the column
     statistics of the rows that are written (engine.path_stats on the kept rows only: every rank holds the genomes and the
-    gathered paths, so no collective is added) and its PAF lines carry the tags of formats.divergence_tags."""
+    gathered paths, so no collective is added) and its PAF lines carry the tags of formats.divergence_tags.  With paths a fifth
+    value follows: (records, first, blocks) of the rows kept, in the order of `kept` — what --regionStats joins with the regions.
+    paf_rows=False: the paths are wanted for that alone, no PAF line is made and the fourth value is empty."""
     dist = dist or Dist()
     none = (np.zeros(0, dtype=engine._ffi.ALIGNMENT), np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=engine._ffi.PATH_BLOCK))
     first = blk = None
@@ -104,13 +106,15 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, 
     rows = []
     blocks, kept = formats.tab_blocks(alns, A.names, QG.names, min_len, min_idt, rows=rows)
     f2, b2 = formats.select_paths(first, blk, rows[0])
+    if not paf_rows:
+        return blocks, int(alns.size), kept, {}, (alns[rows[0]], f2, b2)
     stats = engine.path_stats(A, B, alns[rows[0]], f2, b2) if divergence and dist.rank == 0 else None
     paf = formats.paf_lines(alns[rows[0]], f2, b2, A.names, A.lengths, QG.names, QG.lengths, stats=stats)
     paf_blocks, at = {}, 0
     for pr in sorted(blocks):   # tab_blocks makes its blocks in (tid, qid) order
         paf_blocks[pr] = paf[at:at + len(blocks[pr])]
         at += len(blocks[pr])
-    return blocks, int(alns.size), kept, paf_blocks
+    return blocks, int(alns.size), kept, paf_blocks, (alns[rows[0]], f2, b2)
 
 
 def write_paf(path, pairs, paf_blocks, splitSelf=False):
@@ -136,10 +140,12 @@ def write_tab(path, pairs, blocks, select=None):
                 f.write(line + '\n')
 
 
-def collapse_to_gff(tab_path, names, lengths, min_cov, min_len, source, label, prefix, kept=None):
+def collapse_to_gff(tab_path, names, lengths, min_cov, min_len, source, label, prefix, kept=None, regions_out=None):
     """wrappers.py:1116-1177: TAB -> BED -> depth >= minCov -> merge -> minLen -> GFF rows.  `kept`: the (tid, start1, end1)
     of the rows this process has just written to `tab_path` (tid = index into `names`) — the same numbers the BED projection
-    would read back from the file, without parsing 6e5 lines again; None: read the file (--recycle, imported TABs)."""
+    would read back from the file, without parsing 6e5 lines again; None: read the file (--recycle, imported TABs).
+    regions_out (a list, optional) receives the regions behind the lines, as engine.coverage_collapse returned them
+    (chrom = index into the sorted names)."""
     names_sorted = sorted(names, key=lambda s: s.encode())
     cid = {n: i for i, n in enumerate(names_sorted)}
     length_of = dict(zip(names, lengths))
@@ -151,28 +157,51 @@ def collapse_to_gff(tab_path, names, lengths, min_cov, min_len, source, label, p
     if iv.shape[0] == 0:
         return []
     regions = engine.coverage_collapse(iv, [length_of[n] for n in names_sorted], min_cov, min_len)
+    if regions_out is not None:
+        regions_out.append(regions)
     return formats.gff_repeat_lines(regions, names_sorted, source, label, prefix)
+
+
+def region_stat_block(A, B, kept_paths, select, regions, prefix, header):
+    """--regionStats for one block of GFF3 rows: the rows `select` (a mask) of the kept rows' (records, first, blocks) joined
+    with `regions` (formats.region_items), one engine.window_stats call, the lines of formats.region_stat_lines."""
+    recs, first, blk = kept_paths
+    rows = np.flatnonzero(select)
+    f2, b2 = formats.select_paths(first, blk, rows)
+    names_sorted = sorted(A.names, key=lambda s: s.encode())
+    cid = {n: i for i, n in enumerate(names_sorted)}
+    items, per_region = formats.region_items(recs[rows], regions, [cid[n] for n in A.names], first=f2, blocks=b2, self_job=B is None)
+    stats = engine.window_stats(A, B, recs[rows], f2, b2, items, len(regions))
+    return formats.region_stat_lines(regions, names_sorted, prefix, stats, per_region, header=header)
 
 
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
-                 B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False):
+                 B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
     'path' (or its _ffi.ANCHOR_* number; mimeo_hip.h MIMEO_ANCHOR_*).  bound_extensions: bound every gapped extension by
-    the earlier alignments of its pair and strand (mimeo_params.bound_extensions); ValueError without the path rule."""
+    the earlier alignments of its pair and strand (mimeo_params.bound_extensions); ValueError without the path rule.
+    region_stats: also write, to this file, one line per GFF3 row with the column statistics of the alignment rows that overlap
+    the region, clipped to it (--regionStats; formats.region_stat_lines, kernel K10).  The alignment call then asks for the
+    paths, with or without paf; rank 0 holds the gathered paths and every rank the genomes, so no collective is added.  Nothing
+    is written when the TAB is recycled (there are no paths)."""
     dist = dist or Dist()
+    kept_paths = None
     outtab_intra = outtab + '_intra.tab'
     kept = None
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
-        blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None,
-                                               divergence=divergence and paf is not None)
+        blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None or region_stats is not None,
+                                               divergence=divergence and paf is not None, paf_rows=paf is not None)
+        if region_stats is not None:
+            kept_paths = more[1]
         if paf is not None and dist.rank == 0:
             write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None)
         if len(set(pairs)) != len(pairs):
             kept = None   # a pair listed twice is written twice (the reference would run it twice): read the file back instead
+            kept_paths = None
         if dist.rank == 0:
             if splitSelf:
                 write_tab(outtab, pairs, blocks, select=lambda pr: pr[0] != pr[1])
@@ -186,7 +215,8 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
         intra = kept[:, 0] == kept[:, 1] if B is None else np.zeros(kept.shape[0], bool)
         k_main = kept[~intra][:, [0, 2, 3]] if splitSelf else kept[:, [0, 2, 3]]
         k_intra = kept[intra][:, [0, 2, 3]]
-    lines = collapse_to_gff(outtab, A.names, A.lengths, minCov, minLen, source, str(label), str(prefix), kept=k_main)
+    reg_main, reg_intra = [], []
+    lines = collapse_to_gff(outtab, A.names, A.lengths, minCov, minLen, source, str(label), str(prefix), kept=k_main, regions_out=reg_main)
     if splitSelf:
         if reuseTab and not os.path.isfile(outtab_intra) and os.path.isfile(outtab):
             logging.warning("Warning: Could not find intra-chrom results file: %s \nRe-run in '--strictSelf' "
@@ -194,11 +224,25 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
         else:
             # the reference restarts the ID counter with the same prefix (wrappers.py:1259-1264)
             lines += collapse_to_gff(outtab_intra, A.names, A.lengths, intraCov, minLen, source,
-                                     str(label) + '_intra', str(prefix), kept=k_intra)
+                                     str(label) + '_intra', str(prefix), kept=k_intra, regions_out=reg_intra)
     with open(outgff, 'w') as f:
         f.write(formats.GFF_HEADER + '\n')
         for line in lines:
             f.write(line + '\n')
+    if region_stats is not None:
+        if kept_paths is None:
+            logging.warning('--regionStats needs the alignments\' paths: none with a recycled alignment file or a pair listed twice; %s is not written',
+                            region_stats)
+        else:
+            # the regions of a block take their rows from the TAB the block was collapsed from
+            none = np.zeros(0, dtype=engine._ffi.INTERVAL)
+            split = splitSelf and B is None
+            rl = region_stat_block(A, B, kept_paths, ~intra if split else np.ones(kept.shape[0], bool), reg_main[0] if reg_main else none, str(prefix), True)
+            if split:   # the intra lines follow, with their restarted IDs, as in the GFF3
+                rl += region_stat_block(A, B, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), False)
+            with open(region_stats, 'w') as f:
+                for line in rl:
+                    f.write(line + '\n')
     return lines
 
 
