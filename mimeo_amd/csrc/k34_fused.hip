@@ -19,8 +19,10 @@
 //     the target frame from its owner lane
 //     (ds_bpermute) and the query frame from LDS, and runs the pre-filter: twelve XORs bring the two frames
 //     together, every shift of the popcount bounds and of the earlier-seed-hit test is a compile-time constant;
-//   * the ~4 % of the pairs the filter cannot dismiss go, compacted per wavefront (ballot + prefix count), to the
-//     unit's walk queue (k4_extend_hits on the queue: sharp filter + exact walk, right behind this kernel).
+//   * the ~4 % of the pairs the filter cannot dismiss are staged per wavefront (ballot + prefix count); at the flush the
+//     first pass runs the SHARP filter on the 64 staged pairs (both frames fetched by entry number: pair_needs_walk_sharp)
+//     and only the third that survives goes to the unit's walk queue (k4_walk_batch: the exact walk, right behind
+//     this kernel; the split pass leaves the sharp filter to that kernel).
 // HBM traffic per unit: the two offset arrays, positions + frames of both sides once (52 bytes per entry), and the target
 // frames of a tile once more per further query segment (Infinity Cache).
 #include <cstdio>
@@ -54,7 +56,8 @@ struct FusedArgs {
     HeavyPlan plan;
     int xdrop, hspthresh, transitions;
     uint32_t dbg;  // switch word.  Development (MIMEO_K34_DEBUG): 1 = no pre-filter arithmetic, 2 = nothing is passed on, 4 = no pair
-                   // rounds, 8 = no descriptors either (split pass only: its lane-major emission), 16 = run members are not dropped
+                   // rounds, 8 = no descriptors either (split pass only: its lane-major emission), 16 = run members are not dropped,
+                   // 32 = no sharp filter at the first pass's walk-queue flush (entries go out unmarked, the walk kernel filters them)
 };
 
 // ---- pre-filter on two frames in the common alignment ------------------------------------------------------
@@ -133,6 +136,35 @@ __device__ __forceinline__ bool pair_needs_walk(const uint4 t0, const uint4 t1, 
     return !(L.stop && R.stop && L.ub + R.ub < hspthresh && veto == 0);
 }
 
+// The SHARP filter on two frames: the three proofs of hit_needs_walk<16> (k4_device.h) restated in frame coordinates, run by the
+// first pass where it flushes a wavefront of staged pairs (flush_walk) so that the walk-queue kernel neither gathers a
+// neighbourhood nor shifts it for a pair that comes to nothing.  The 16-step blocks are half-words at compile-time
+// positions — left steps 0 .. 79 = word 3, word 2 and the upper half of word 1 from bit 31 downwards, right steps
+// 0 .. 63 = words 4 and 5 from bit 0 upwards — with the class-exact bounds of bound_window (transversions, transitions,
+// C/G matches from dl, dh and the target's lo ^ hi).  The earlier-seed-hit test is the exact 12of19 rule with the
+// transition plane on steps 0 .. 63, and on steps 64 .. 79 (word 0 holds their windows) unless the left stop was proven within 64
+// steps: no seed-validity planes, so still a superset.  true = the pair is walked exactly.
+__device__ __forceinline__ bool pair_needs_walk_sharp(const uint4 t0, const uint4 t1, const uint4 t2, const uint4 q0, const uint4 q1,
+                                                      const uint4 q2, int xdrop, int hspthresh, int transitions) {
+    // planes: lo = {0.x 0.y 0.z 0.w 1.x 1.y}, hi = {1.z 1.w 2.x 2.y 2.z 2.w}
+    const uint32_t dl0 = t0.x ^ q0.x, dl1 = t0.y ^ q0.y, dl2 = t0.z ^ q0.z, dl3 = t0.w ^ q0.w, dl4 = t1.x ^ q1.x, dl5 = t1.y ^ q1.y;
+    const uint32_t dh0 = t1.z ^ q1.z, dh1 = t1.w ^ q1.w, dh2 = t2.x ^ q2.x, dh3 = t2.y ^ q2.y, dh4 = t2.z ^ q2.z, dh5 = t2.w ^ q2.w;
+    const uint32_t n0 = dl0 | dh0, n1 = dl1 | dh1, n2 = dl2 | dh2, n3 = dl3 | dh3;
+    // earlier seed hits: starts 77..108 <-> left steps 31..0, 45..76 <-> steps 63..32, 29..44 <-> steps 79..64 (bits 31..16 of h2)
+    const uint32_t h0 = seed_starts32<CARE19, true>(n2, n3, dl2, dl3, transitions);
+    const uint32_t h1 = seed_starts32<CARE19, true>(n1, n2, dl1, dl2, transitions);
+    const uint32_t h2 = seed_starts32<CARE19, true>(n0, n1, dl0, dl1, transitions) & 0xFFFF0000u;
+    Bound L{0, 0, 0, 0, false}, R{0, 0, 0, 0, false};
+    bound_window<16, true>(L, dl3, dh3, t0.w ^ t2.y, xdrop);      // left steps 0 .. 31
+    bound_window<16, true>(L, dl2, dh2, t0.z ^ t2.x, xdrop);      // 32 .. 63
+    const bool stop64 = L.stop;
+    bound_window<16, true, 1>(L, dl1, dh1, t0.y ^ t1.w, xdrop);   // 64 .. 79: their boundaries only matter when no stop was proven before
+    bound_window<16, false>(R, dl4, dh4, t1.x ^ t2.z, xdrop);     // right steps 0 .. 31
+    bound_window<16, false>(R, dl5, dh5, t1.y ^ t2.w, xdrop);     // 32 .. 63
+    const uint32_t veto = h0 | h1 | (stop64 ? 0u : h2);
+    return !(L.stop && R.stop && L.ub + R.ub < hspthresh && veto == 0);
+}
+
 // Split pass only (the tiles microsatellites and high-copy repeats fill): is this pair an INTERIOR member of a run of consecutive
 // seed hits of its diagonal — exact seed hits one and two positions back and one ahead (k4_device.h, "runs of consecutive seed
 // hits")?  Such a hit leaves no record anywhere, so it is dropped here, before the pre-filter and the walk queue.  The three
@@ -208,19 +240,35 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
     uint2 *s_walk = s_walk_all + wv * 64;
     uint32_t n_walk = 0;
 
-    // the pairs the filter passed on go to the batch's walk queue, 64 at a time (one atomic per flush)
+    // the pairs the filter passed on go to the batch's walk queue, 64 at a time (one atomic per flush).  A staged pair names its two
+    // index ENTRIES: the positions of all 64 are fetched here, one gather per flush instead of one per round, and — first pass —
+    // so are the two frames (six 16-byte loads per lane from arrays this workgroup has just streamed) for the sharp filter: the
+    // staged pairs are a full wavefront of compacted work, the other wavefronts of the CU hide the gather, and only the
+    // survivors are appended, marked in bit 31 of x (WALK_SHARP_DONE: the walk kernel does not filter them again)
     auto flush_walk = [&](uint32_t n) {
         __builtin_amdgcn_wave_barrier();
-        unsigned long long b = 0;
         // (split pass: the 64 workgroups that share a tile have one blockIdx.x — spread them, or a microsatellite tile fills one shard)
         const uint32_t shard = (HEAVY ? blockIdx.x + part_no : blockIdx.x) & 7u;
-        if (lane == 0) b = atomicAdd(&A.q.nwalk_u[(size_t)ai * 8 + shard], (unsigned long long)n);
-        b = __shfl(b, 0);
-        // (a staged pair names its query ENTRY: the positions of all 64 are fetched here, one gather per flush instead of one per round)
-        if (lane < n && b + lane < U.walk_cap) {
-            uint2 e = s_walk[lane];
-            e.y = U.Q.pos[e.y] & POS_MASK;
-            A.q.walkq[U.walk_base + (size_t)shard * U.walk_cap + b + lane] = e;
+        uint2 e = make_uint2(0, 0);
+        bool keep = lane < n;
+        if (keep) {
+            const uint2 s = s_walk[lane];
+            const uint32_t tp = U.T.pos[s.x], qp = U.Q.pos[s.y];
+            e = make_uint2(tp & POS_MASK, qp & POS_MASK);
+            if (!HEAVY && !(A.dbg & 32u)) {
+                const gptr<uint4> tf = U.T.fr + s.x, qf = U.Q.fr + s.y;
+                const uint4 ta = tf[0], tb = tf[U.T.fr_stride], tc = tf[2 * (size_t)U.T.fr_stride];
+                const uint4 qa = qf[0], qb = qf[U.Q.fr_stride], qc = qf[2 * (size_t)U.Q.fr_stride];
+                keep = ((tp | qp) & POS_NFLAG) != 0 || pair_needs_walk_sharp(ta, tb, tc, qa, qb, qc, A.xdrop, A.hspthresh, A.transitions);
+                e.x |= WALK_SHARP_DONE;
+            }
+        }
+        const uint64_t km = __ballot(keep);
+        if (km) {
+            unsigned long long b = 0;
+            if (lane == 0) b = atomicAdd(&A.q.nwalk_u[(size_t)ai * 8 + shard], (unsigned long long)__popcll(km));
+            b = __shfl(b, 0) + __popcll(km & lt_mask);
+            if (keep && b < U.walk_cap) A.q.walkq[U.walk_base + (size_t)shard * U.walk_cap + b] = e;
         }
         __builtin_amdgcn_wave_barrier();
     };
@@ -308,8 +356,8 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
             if (e < nT) { nf0 = tF0[e]; nf1 = tF1[e]; nf2 = tF2[e]; npos = U.T.pos[t0 + e]; }
         }
         unsigned long long hits_acc = 0;   // pairs this wavefront enumerates in this tile (wave-uniform): the tile's exact hit count
-        // 64 pairs, one per lane: the target entry's frame and position, the query entry qi of the current segment (first entry qs)
-        auto pair_round = [&](const bool valid, const uint4 ta, const uint4 tb, const uint4 tc, const uint32_t tpf, const uint32_t qi, const uint32_t qs) {
+        // 64 pairs, one per lane: the target entry te (number in the index), its frame and position, the query entry qi of the current segment (first entry qs)
+        auto pair_round = [&](const bool valid, const uint4 ta, const uint4 tb, const uint4 tc, const uint32_t tpf, const uint32_t te, const uint32_t qi, const uint32_t qs) {
             const uint4 qa = sQF[qi], qb = sQF[QSEG + qi], qc = sQF[2 * QSEG + qi];
             const uint32_t qflag = sQN[qi];
             bool need = false;
@@ -343,7 +391,7 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
             if (m) {
                 const uint32_t add = (uint32_t)__popcll(m);
                 if (n_walk + add > 64u) { flush_walk(n_walk); n_walk = 0; }
-                if (need) s_walk[n_walk + __popcll(m & lt_mask)] = make_uint2(tpf & POS_MASK, q0 + qs + qi);   // the query entry: flush_walk looks its position up
+                if (need) s_walk[n_walk + __popcll(m & lt_mask)] = make_uint2(te, q0 + qs + qi);   // the two entries: flush_walk looks their positions up
                 n_walk += add;
             }
         };
@@ -431,7 +479,7 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
                         if (!(A.dbg & 4u)) {
                             const uint4 ta = bperm4(owner, f0), tb = bperm4(owner, f1), tc = bperm4(owner, f2);
                             const uint32_t tpf = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(owner << 2), (int)mypos);
-                            pair_round(valid, ta, tb, tc, tpf, qi, qs);
+                            pair_round(valid, ta, tb, tc, tpf, t0 + e0 + owner, qi, qs);
                         }
                         __builtin_amdgcn_wave_barrier();
                         head = (head + 64u) & (RING - 1u);
@@ -518,7 +566,7 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
                             // the target frame lives in its owner lane's registers, the query frame in LDS
                             const uint4 ta = bperm4(owner, f0), tb = bperm4(owner, f1), tc = bperm4(owner, f2);
                             const uint32_t tpf = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(owner << 2), (int)mypos);
-                            pair_round(valid, ta, tb, tc, tpf, qi, qs);
+                            pair_round(valid, ta, tb, tc, tpf, t0 + e0 + owner, qi, qs);
                         }
                         __builtin_amdgcn_wave_barrier();
                     }
@@ -538,7 +586,7 @@ __global__ __launch_bounds__(THREADS, 4) void k34_scan_extend(FusedArgs A) {
                             if (A.dbg & 4u) continue;
                             for (uint32_t i = a; i < b; i += 64u) {
                                 const bool valid = i + lane < b;
-                                pair_round(valid, ta, tb, tc, tpf, valid ? i + lane : a, qs);
+                                pair_round(valid, ta, tb, tc, tpf, t0 + e0 + (uint32_t)o, valid ? i + lane : a, qs);
                             }
                         }
                     }

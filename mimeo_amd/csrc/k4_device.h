@@ -51,7 +51,7 @@ struct ExtQueues {
     uint32_t *fprev;
     uint2 *medq, *longq;      // hits whose walk outlives the frame / LONG_WINDOWS windows
     uint32_t *medu, *longu;   // ... and their units
-    uint2 *walkq;             // hits that the pre-filter of K34 could not dismiss: a region of eight shards per unit (FusedUnit)
+    uint2 *walkq;             // hits that the filters of K34 could not dismiss (x: tpos, WALK_SHARP_DONE in bit 31; y: qpos): a region of eight shards per unit (FusedUnit)
     unsigned long long *nwalk_u;    // ... entries per unit and shard (workgroup number mod 8, i.e. per XCD)
     unsigned long long *nheavy_u;   // tiles per unit that K34's first pass left to its split pass
     uint32_t *heavy;                // ... their numbers: NTILE slots per unit
@@ -63,6 +63,10 @@ struct ExtQueues {
     uint64_t cand_cap, follow_cap, med_cap, long_cap, walk_cap;   // follow_cap, med_cap, walk_cap: per shard (shard r = base[r * cap ...])
     uint32_t ebits, dbits;
 };
+// bit 31 of a walk-queue entry's x (POS_MASK leaves it free): K34's first pass ran the sharp filter on this pair at its flush and
+// could not dismiss it — the walk kernel walks it without filtering again.  Unmarked entries (split pass, MIMEO_K34_DEBUG & 32) are
+// filtered there as before.
+constexpr uint32_t WALK_SHARP_DONE = 0x80000000u;
 __device__ __forceinline__ uint32_t queue_shard() { return blockIdx.x & 7u; }
 // a slot of an append-only queue for every lane that calls this together: one atomic per wavefront (same-address
 // atomics serialise at ~13 ns each)

@@ -242,14 +242,22 @@ __device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GSt
             }
             h = hits[at];
         }
+        // a walk-queue entry that K34's first pass has put through its sharp filter already (WALK_SHARP_DONE) is not filtered
+        // again; the mark comes off before anything else uses the position
+        const bool marked = nhits_dev && (h.x & WALK_SHARP_DONE) != 0;
+        if (nhits_dev) h.x &= POS_MASK;
         const bool valid = gid < nhits && !(skip_diag0 && h.x == h.y);  // the main diagonal of a self unit belongs to k4_diag0
         if (!FILTER) {
             walk_batch(valid, h, false);
         } else {
-            bool need = false;
-            if (valid)
-                need = VARIANT == 9 ? hit_needs_walk<16, true>(T, Q, h, xdrop, hspthresh, transitions)
-                                    : hit_needs_walk<16, false>(T, Q, h, xdrop, hspthresh, transitions);
+            bool need = valid && marked;
+            // (no lane with an unmarked entry — every wavefront of a queue the first pass filled alone: the filter and its
+            // thirteen loads are skipped wave-uniformly)
+            if (__ballot(valid && !marked)) {
+                if (valid && !marked)
+                    need = VARIANT == 9 ? hit_needs_walk<16, true>(T, Q, h, xdrop, hspthresh, transitions)
+                                        : hit_needs_walk<16, false>(T, Q, h, xdrop, hspthresh, transitions);
+            }
             const uint64_t m = __ballot(need);
             if (m) {
                 const uint32_t add = (uint32_t)__popcll(m);
