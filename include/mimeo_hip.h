@@ -412,6 +412,43 @@ int mimeo_path_window_stats(const mimeo_genome *T, const mimeo_genome *Q /* NULL
                             mimeo_window_stats *out /* caller's, ngroups entries */);
 
 /*
+ * The text of alignment paths (kernel K11): the two rows of every pairwise alignment, target over query, as letters — what a
+ * MAF block or a cs:Z: tag is written from, and the way to read a single aligned base.  The host holds no sequence text
+ * (the FASTA is streamed to the device); the rows are made on the device from the resident genomes.
+ *
+ * T, Q, aln, n, path_first, blocks and nblocks are those of mimeo_path_stats, and so is every check: a violation is
+ * MIMEO_ERR_ARG before anything is uploaded, with a message that starts with "mimeo_path_text:" and names the record and the
+ * block.  Of a record only tid, qid and qstrand are read.  With X the target's forward strand and Y the query's forward
+ * strand for qstrand == 0, its stored reverse complement for qstrand == 1 (the coordinates of mimeo_path_block; nothing is
+ * flipped), row i is trow[row_first[i] .. row_first[i + 1]) over the same range of qrow: two rows of equal length, no
+ * padding, no terminator.  For the blocks b_0 .. b_{m-1} of the path, in order:
+ *   between blocks  for k > 0, with dq = b_k.q - (b_{k-1}.q + b_{k-1}.len) and dt likewise: first dq insertion columns, '-'
+ *                   in trow over the query bases Y[b_{k-1}.q + b_{k-1}.len + j] in qrow; then dt deletion columns, the
+ *                   target bases in trow over '-' in qrow.  Insertions before deletions: the order of a CIGAR's I and D
+ *                   and of mimeo_path_window_stats;
+ *   every block     b_k.len columns of X[b_k.t + j] over Y[b_k.q + j];
+ *   letters         A C G T in upper case where the base is one of ACGT, N for every other base (the N plane decides first,
+ *                   as for mimeo_path_stats).  The device keeps neither case nor IUPAC codes: a soft-masked 'a' comes out
+ *                   'A', and 'R' or 'n' comes out 'N'.
+ * An alignment without blocks has zero columns.
+ *
+ * What a caller may rely on:
+ *   - row_first[i + 1] - row_first[i] = (t_end - t_first) + (q_end - q_first) - the sum of len, in 64 bits;
+ *   - the bytes of trow that are not '-' are the target slice, those of qrow the slice of the aligned strand;
+ *   - the columns where both bytes are equal and neither 'N' nor '-' number exactly `matches` of mimeo_path_stats;
+ *   - the bytes depend on nothing but the sequences and the blocks.
+ * row_first (n + 1 entries), trow and qrow (row_first[n] bytes each) are allocated by the library and released with
+ * mimeo_free.  n == 0 returns MIMEO_OK with row_first holding one zero; where there is no column at all, trow and qrow are
+ * NULL.  The rows pass through device buffers in slices of bounded size, so a job of any size runs in the memory that is free
+ * next to the genomes; the host arrays hold the whole call, and a caller bounds those by what it asks for in one call.
+ *
+ * A new symbol beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs it checks for the symbol.
+ */
+int mimeo_path_text(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, const mimeo_alignment *aln, uint64_t n,
+                    const uint64_t *path_first, const mimeo_path_block *blocks, uint64_t nblocks,
+                    uint64_t **row_first /* n + 1 */, uint8_t **trow, uint8_t **qrow /* row_first[n] bytes each */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  mimeo_last_error() describes the last one.

@@ -54,6 +54,16 @@ def add_common(parser, prog, gff_default, label, prefix, with_b):
                              'tv:i: (transitions, transversions) and kd:f: (Kimura two-parameter distance; left out where undefined), '
                              'counted on the GPU from the alignment\'s columns. An error without --paf. Ignored with --recycle when the '
                              'alignment file exists.')
+    parser.add_argument('--maf', type=str, default=None, metavar='FILE',
+                        help='Also write the rows of the alignment file as MAF to FILE, one block per row in the same order: the '
+                             'alignment itself as text, target over query, made on the GPU from the resident genomes. The letters are '
+                             'A C G T in upper case and N for everything else: the engine keeps neither case nor IUPAC codes, so a '
+                             'soft-masked a is written A, and R or n is written N. Does not need --paf. Nothing is written with '
+                             '--recycle when the alignment file exists.')
+    parser.add_argument('--cs', action='store_true', default=False,
+                        help='With --paf: every PAF row also carries minimap2\'s short cs:Z: tag behind cg:Z: (:n matches, *xy a '
+                             'substitution or a column with an n, +seq / -seq inserted and deleted bases; target as the reference, lower '
+                             'case, n for everything that is not ACGT). An error without --paf.')
 
 
 def add_region_stats(parser):
@@ -73,6 +83,8 @@ def check_common(parser, args):
         parser.error('--boundExtensions needs --anchorRule path')
     if args.divergence and not args.paf:
         parser.error('--divergence needs --paf')
+    if args.cs and not args.paf:
+        parser.error('--cs needs --paf')
     return args
 
 

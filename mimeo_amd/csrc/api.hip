@@ -398,6 +398,20 @@ int mimeo_path_window_stats(const mimeo_genome *T, const mimeo_genome *Q, const 
     return window_stats_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, items, nitems, ngroups, out);
 }
 
+int mimeo_path_text(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first,
+                    const mimeo_path_block *blocks, uint64_t nblocks, uint64_t **row_first, uint8_t **trow, uint8_t **qrow) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!row_first || !trow || !qrow) { set_error("mimeo_path_text: null argument"); return MIMEO_ERR_ARG; }
+    *row_first = nullptr; *trow = nullptr; *qrow = nullptr;
+    if (n && (!T || !aln || !path_first || (nblocks && !blocks))) { set_error("mimeo_path_text: null argument"); return MIMEO_ERR_ARG; }
+    if (!n) {   // one zero, and two empty rows
+        if (!(*row_first = (uint64_t *)calloc(1, sizeof(uint64_t)))) { set_error("mimeo_path_text: out of host memory"); return MIMEO_ERR_NOMEM; }
+        return MIMEO_OK;
+    }
+    return path_text_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, row_first, trow, qrow);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

@@ -342,5 +342,8 @@ int path_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_
 int window_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
                         const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_window_item *items, uint64_t nitems, uint64_t ngroups,
                         mimeo_window_stats *out);
+// K11: the two rows of every alignment as letters (k11_path_text.hip); host in, three malloc'ed arrays out.  Q is never null here.
+int path_text_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
+                     const mimeo_path_block *blocks, uint64_t nblocks, uint64_t **row_first, uint8_t **trow, uint8_t **qrow);
 
 }  // namespace mimeo

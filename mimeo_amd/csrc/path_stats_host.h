@@ -15,23 +15,25 @@ namespace path_stats_host {
 
 // Everything the kernel relies on, checked before anything is uploaded.  All arithmetic in 64 bits: t = 0xFFFFFFF0 with
 // len = 0x20 is beyond every scaffold, not at base 0x10.  len_t / len_q: bases per scaffold of the target and of the query
-// genome.  Returns true when the call is sound; otherwise *msg names the record (and the block) that is not.
+// genome.  Returns true when the call is sound; otherwise *msg names the record (and the block) that is not.  `name`: the entry
+// point the message starts with (mimeo_path_text makes the same checks under its own name).
 inline bool validate(const std::vector<uint64_t> &len_t, const std::vector<uint64_t> &len_q, const mimeo_alignment *aln, uint64_t n,
-                     const uint64_t *first, const mimeo_path_block *blocks, uint64_t nblocks, std::string *msg) {
+                     const uint64_t *first, const mimeo_path_block *blocks, uint64_t nblocks, std::string *msg,
+                     const char *name = "mimeo_path_stats") {
     char buf[320];
     auto fail = [&](const char *what, uint64_t rec, bool has_block, uint64_t blk) {
         if (has_block) {
             const mimeo_path_block &b = blocks[blk];
-            snprintf(buf, sizeof buf, "mimeo_path_stats: record %llu, block %llu (t %u, q %u, len %u): %s", (unsigned long long)rec,
+            snprintf(buf, sizeof buf, "%s: record %llu, block %llu (t %u, q %u, len %u): %s", name, (unsigned long long)rec,
                      (unsigned long long)blk, b.t, b.q, b.len, what);
         } else {
-            snprintf(buf, sizeof buf, "mimeo_path_stats: record %llu: %s", (unsigned long long)rec, what);
+            snprintf(buf, sizeof buf, "%s: record %llu: %s", name, (unsigned long long)rec, what);
         }
         *msg = buf;
         return false;
     };
     if (!n) return true;
-    if (!aln || !first || (nblocks && !blocks)) { *msg = "mimeo_path_stats: null argument"; return false; }
+    if (!aln || !first || (nblocks && !blocks)) { *msg = std::string(name) + ": null argument"; return false; }
     // the offsets first: no block is looked at before every range is known to lie inside blocks[0 .. nblocks)
     if (first[0] != 0) return fail("path_first[0] is not 0", 0, false, 0);
     for (uint64_t i = 0; i < n; i++)

@@ -224,6 +224,28 @@ def window_stats(A, B, records, first, blocks, items, ngroups):
     return out
 
 
+def path_text(A, B, records, first, blocks):
+    """The text of alignment paths (mimeo_path_text, kernel K11): (row_first, trow, qrow) as numpy arrays (<u8, uint8, uint8).
+    Row i is trow[row_first[i]:row_first[i + 1]] over the same range of qrow: the target's letters over the aligned query
+    strand's, '-' where the other sequence jumps (insertions before deletions), A C G T and N for everything else — the device
+    keeps neither case nor IUPAC codes (include/mimeo_hip.h has the rules).  records / first / blocks and the errors as for
+    path_stats.  The arrays hold the whole call: a caller bounds them by what it asks for at once (workflow.text_runs)."""
+    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
+    if first.size != recs.size + 1:
+        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_path_text'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_path_text: rebuild the library')
+    pf, pt, pq = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _ffi.check(lib.mimeo_path_text(A._h, B._h if B is not None else None, recs.ctypes.data if recs.size else None, recs.size, first.ctypes.data,
+                                   blk.ctypes.data if blk.size else None, blk.size, C.byref(pf), C.byref(pt), C.byref(pq)))
+    row_first = _ffi.take(pf, C.c_uint64(recs.size + 1), np.dtype('<u8'))
+    total = C.c_uint64(int(row_first[-1]))
+    return row_first, _ffi.take(pt, total, np.dtype(np.uint8)), _ffi.take(pq, total, np.dtype(np.uint8))
+
+
 def failed_pairs():
     """Pairs of the last align_pairs / align_units call that hit a documented limit and were left out (the reference's script
     loses only the failing lastz run's rows: utils.py:125-128): [(index into the call's pair list, error code)]."""

@@ -203,13 +203,99 @@ def select_paths(first, blocks, rows):
     return out, blocks[take]
 
 
-def paf_lines(records, first, blocks, tnames, tlens, qnames, qlens, stats=None):
+def path_columns(first, blocks):
+    """Columns of every alignment's row (engine.path_text: row_first[i + 1] - row_first[i]) from the paths alone, as int64:
+    (t_end - t_first) + (q_end - q_first) - sum of len; 0 without blocks."""
+    first = np.asarray(first, dtype=np.int64)
+    t, q, ln = blocks['t'].astype(np.int64), blocks['q'].astype(np.int64), blocks['len'].astype(np.int64)
+    s = np.concatenate([np.zeros(1, np.int64), np.cumsum(ln)])
+    out = np.zeros(first.size - 1, dtype=np.int64)
+    some = np.flatnonzero(first[1:] > first[:-1])
+    a, z = first[:-1][some], first[1:][some] - 1
+    out[some] = (t[z] + ln[z] - t[a]) + (q[z] + ln[z] - q[a]) - (s[z + 1] - s[a])
+    return out
+
+
+MAF_HEADER = '##maf version=1 scoring=mimeo-amd'
+
+
+def maf_lines(records, row_first, trow, qrow, first, blocks, tnames, tlens, qnames, qlens):
+    """One MAF block per record, as one string of three lines (a file writes it and a newline, which is the empty line that
+    ends a block):
+      a score=<score>
+      s <tname> <tstart> <tend - tstart> + <tlen> <trow>
+      s <qname> <start> <qend - qstart> <+|-> <qlen> <qrow>
+    Row i is trow[row_first[i]:row_first[i + 1]] over the same range of qrow (engine.path_text); the path of record i is
+    blocks[first[i]:first[i + 1]].  The query start is on the aligned strand, MAF's own convention for a '-' row: the q of the
+    path's first block, which is qlen - qend of the record (without blocks: qstart, or qlen - qend).  The letters are the
+    engine's: upper case, N for everything that is not ACGT."""
+    out = []
+    for i in range(len(records)):
+        r = records[i]
+        t, q, minus = int(r['tid']), int(r['qid']), int(r['qstrand']) != 0
+        a, z = int(row_first[i]), int(row_first[i + 1])
+        if int(first[i + 1]) > int(first[i]):
+            qs = int(blocks[int(first[i])]['q'])
+        else:
+            qs = int(qlens[q]) - int(r['qend']) if minus else int(r['qstart'])
+        out.append('a score=%d\ns %s %d %d + %d %s\ns %s %d %d %s %d %s\n' % (
+            int(r['score']), tnames[t], int(r['tstart']), int(r['tend']) - int(r['tstart']), int(tlens[t]), bytes(trow[a:z]).decode('ascii'),
+            qnames[q], qs, int(r['qend']) - int(r['qstart']), '-' if minus else '+', int(qlens[q]), bytes(qrow[a:z]).decode('ascii')))
+    return out
+
+
+_ACGT = np.zeros(256, dtype=bool)
+_ACGT[list(b'ACGT')] = True
+
+
+def cs_tag(trow_i, qrow_i):
+    """minimap2's short cs of ONE alignment from its two rows (engine.path_text), the target as the reference:
+      :<n>    a maximal run of matches — columns of equal letters, both of ACGT (the matches of engine.path_stats)
+      *<x><y> one column of any other aligned pair: target letter, query letter, lower case; 'n' is a letter here, so N over N
+              is *nn and never part of a ':' run
+      +<seq>  an insertion run (query bases absent from the target), -<seq> a deletion run, lower case
+    The ':' lengths sum to id_n, and the tag walks the columns of cg:Z:.  A run-length encoding of four column classes: the work
+    per column is numpy's."""
+    t, q = np.asarray(trow_i, dtype=np.uint8), np.asarray(qrow_i, dtype=np.uint8)
+    if t.size != q.size:
+        raise ValueError('rows of %d and %d columns' % (t.size, q.size))
+    if t.size == 0:
+        return ''
+    cls = np.ones(t.size, dtype=np.int8)               # 1: a mismatch, or a column with an N
+    cls[(t == q) & _ACGT[t]] = 0                       # 0: match
+    cls[t == 0x2D] = 2                                 # 2: insertion
+    cls[q == 0x2D] = 3                                 # 3: deletion
+    cut = np.flatnonzero(cls[1:] != cls[:-1]) + 1
+    starts, ends = np.concatenate([[0], cut]), np.concatenate([cut, [t.size]])
+    tl, ql = t | 0x20, q | 0x20                        # letters to lower case ('-' is in no run that prints it from its own row)
+    out = []
+    for a, z, c in zip(starts.tolist(), ends.tolist(), cls[starts].tolist()):
+        if c == 0:
+            out.append(':%d' % (z - a))
+        elif c == 1:
+            sub = np.empty((z - a, 3), dtype=np.uint8)
+            sub[:, 0], sub[:, 1], sub[:, 2] = 0x2A, tl[a:z], ql[a:z]
+            out.append(sub.tobytes().decode('ascii'))
+        elif c == 2:
+            out.append('+' + ql[a:z].tobytes().decode('ascii'))
+        else:
+            out.append('-' + tl[a:z].tobytes().decode('ascii'))
+    return ''.join(out)
+
+
+def cs_tags(row_first, trow, qrow):
+    """cs_tag of every row of an engine.path_text result"""
+    return [cs_tag(trow[int(row_first[i]):int(row_first[i + 1])], qrow[int(row_first[i]):int(row_first[i + 1])]) for i in range(len(row_first) - 1)]
+
+
+def paf_lines(records, first, blocks, tnames, tlens, qnames, qlens, stats=None, cs=None):
     """One PAF row per record: query name, length, start, end (0-based half-open, query plus strand), strand, target name,
     length, start, end, residue matches (id_n), alignment length (id_d + gap bases), 255 (no mapping quality), then
     AS:i:<score> and cg:Z:<cigar>.  The path of record i is blocks[first[i]:first[i + 1]] (mimeo_hip.h,
     mimeo_align_units_paths): t on the target plus strand, q on the aligned strand, so the CIGAR of a '-' row runs along the
     target forward and the reverse-complemented query — PAF's own meaning.  stats (one row of engine.path_stats per record;
-    --divergence): the tags of divergence_tags between AS:i: and cg:Z:."""
+    --divergence): the tags of divergence_tags between AS:i: and cg:Z:.  cs (one cs_tag per record; --cs): cs:Z:<tag> follows
+    cg:Z:, so that a row without it is a prefix of the row with it."""
     lines = []
     for i in range(len(records)):
         r = records[i]
@@ -219,7 +305,7 @@ def paf_lines(records, first, blocks, tnames, tlens, qnames, qlens, stats=None):
         lines.append('%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\t%scg:Z:%s' % (
             qnames[q], int(qlens[q]), int(r['qstart']), int(r['qend']), '-' if int(r['qstrand']) else '+', tnames[t], int(tlens[t]),
             int(r['tstart']), int(r['tend']), int(r['id_n']), int(r['id_d']) + gaps, int(r['score']),
-            divergence_tags(stats[i]) + '\t' if stats is not None else '', cigar(b)))
+            divergence_tags(stats[i]) + '\t' if stats is not None else '', cigar(b)) + ('\tcs:Z:' + cs[i] if cs is not None else ''))
     return lines
 
 

@@ -35,7 +35,7 @@ def main(argv=None):
                           minCov=args.minCov, reuseTab=args.recycle, label=args.label, prefix=args.prefix, dist=dist,
                           source='mimeo', B=B, anchor_rule=args.anchorRule,
                           bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence,
-                          region_stats=args.regionStats)
+                          region_stats=args.regionStats, maf=args.maf, cs=args.cs)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

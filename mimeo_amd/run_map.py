@@ -38,7 +38,7 @@ def main(argv=None):
         sys.exit(1)
     workflow.map_hits(A, B, pairs, outtab, minIdt=args.minIdt, minLen=args.minLen, hspthresh=args.hspthresh,
                       reuseTab=args.recycle, dist=dist, anchor_rule=args.anchorRule,
-                      bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence)
+                      bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence, maf=args.maf, cs=args.cs)
     if dist.rank == 0:
         logging.info('Importing alignments from %s' % outtab)
         rows = formats.parse_tab(outtab)

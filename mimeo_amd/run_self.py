@@ -36,7 +36,7 @@ def main(argv=None):
                           minCov=args.minCov, intraCov=args.intraCov, splitSelf=args.strictSelf, reuseTab=args.recycle,
                           label=args.label, prefix=args.prefix, dist=dist,
                           anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence,
-                          region_stats=args.regionStats)
+                          region_stats=args.regionStats, maf=args.maf, cs=args.cs)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

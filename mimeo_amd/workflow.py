@@ -61,7 +61,8 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, 
     their order.  divergence=True (--divergence, with paths): rank 0, which writes the file, also asks the engine for the column
     statistics of the rows that are written (engine.path_stats on the kept rows only: every rank holds the genomes and the
     gathered paths, so no collective is added) and its PAF lines carry the tags of formats.divergence_tags.  With paths a fifth
-    value follows: (records, first, blocks) of the rows kept, in the order of `kept` — what --regionStats joins with the regions.
+    value follows: (records, first, blocks) of the rows kept, in the order of `kept` — what --regionStats joins with the regions
+    and what --maf and --cs ask the engine's text for (write_maf, write_paf).
     paf_rows=False: the paths are wanted for that alone, no PAF line is made and the fourth value is empty."""
     dist = dist or Dist()
     none = (np.zeros(0, dtype=engine._ffi.ALIGNMENT), np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=engine._ffi.PATH_BLOCK))
@@ -117,16 +118,89 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, 
     return blocks, int(alns.size), kept, paf_blocks, (alns[rows[0]], f2, b2)
 
 
-def write_paf(path, pairs, paf_blocks, splitSelf=False):
+TEXT_BUDGET = 1 << 26   # columns of alignment text asked of the engine at once by the writers: two rows of 64 MiB
+
+
+def file_order(pairs, blocks, splitSelf=False):
+    """The kept rows (numbered as align_blocks returns them: pair by pair in sorted (t, q) order, the order of each TAB block)
+    in the order the files list them: pair by pair as write_tab / write_paf go through `pairs`, with --strictSelf the
+    same-scaffold rows behind the others."""
+    at, start = 0, {}
+    for pr in sorted(blocks):
+        start[pr] = at
+        at += len(blocks[pr])
+    out = []
+    for intra in ((False, True) if splitSelf else (None,)):
+        for pr in pairs:
+            if intra is not None and (pr[0] == pr[1]) != intra:
+                continue
+            if pr in start:
+                out.append(np.arange(start[pr], start[pr] + len(blocks[pr]), dtype=np.int64))
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+
+
+def text_runs(columns, budget):
+    """Cut rows 0 .. len(columns) into runs [i0, i1) of consecutive rows whose columns add up to at most `budget`; a single
+    longer row goes alone."""
+    runs, i0, n = [], 0, len(columns)
+    while i0 < n:
+        i1, c = i0 + 1, int(columns[i0])
+        while i1 < n and c + int(columns[i1]) <= budget:
+            c += int(columns[i1])
+            i1 += 1
+        runs.append((i0, i1))
+        i0 = i1
+    return runs
+
+
+def path_text_runs(A, B, kept_paths, order, budget=TEXT_BUDGET):
+    """The alignment text of the rows `order` of kept_paths = (records, first, blocks), run by run (text_runs): yields
+    (j0, j1, records, first, blocks, row_first, trow, qrow) for order[j0:j1], one engine.path_text call each, so that the host
+    never holds more than about `budget` columns of text — a chromosome-long self diagonal is half a gigabyte of rows, and a
+    large job's rows do not fit in memory at once.  What is yielded depends on the rows alone, not on the budget."""
+    recs, first, blk = kept_paths
+    f2, b2 = formats.select_paths(first, blk, order)
+    r2 = recs[order]
+    for j0, j1 in text_runs(formats.path_columns(f2, b2), budget):
+        k0, k1 = int(f2[j0]), int(f2[j1])
+        fr, br = f2[j0:j1 + 1] - f2[j0], b2[k0:k1]
+        yield (j0, j1, r2[j0:j1], fr, br) + tuple(engine.path_text(A, B, r2[j0:j1], fr, br))
+
+
+def write_paf(path, pairs, paf_blocks, splitSelf=False, cs=None):
     """--paf: the PAF row of every row of the TAB, in the TAB's order (write_tab); with --strictSelf the rows of the
-    same-scaffold TAB follow those of the main one.  No header: PAF has none."""
+    same-scaffold TAB follow those of the main one.  No header: PAF has none.  cs (--cs): (A, B, kept_paths, blocks, budget)
+    — every row also ends in cs:Z: (formats.cs_tag), made from the engine's alignment text run by run (path_text_runs)."""
+    lines = []
+    for intra in ((False, True) if splitSelf else (None,)):
+        for pr in pairs:
+            if intra is not None and (pr[0] == pr[1]) != intra:
+                continue
+            lines.extend(paf_blocks.get(pr, ()))
     with open(path, 'w') as f:
-        for intra in ((False, True) if splitSelf else (None,)):
-            for pr in pairs:
-                if intra is not None and (pr[0] == pr[1]) != intra:
-                    continue
-                for line in paf_blocks.get(pr, ()):
-                    f.write(line + '\n')
+        if cs is None:
+            for line in lines:
+                f.write(line + '\n')
+            return
+        A, B, kept_paths, blocks, budget = cs
+        order = file_order(pairs, blocks, splitSelf)
+        assert order.size == len(lines)
+        for j0, j1, _, _, _, row_first, trow, qrow in path_text_runs(A, B, kept_paths, order, budget):
+            for line, tag in zip(lines[j0:j1], formats.cs_tags(row_first, trow, qrow)):
+                f.write(line + '\tcs:Z:' + tag + '\n')
+
+
+def write_maf(path, A, B, pairs, blocks, kept_paths, splitSelf=False, budget=TEXT_BUDGET):
+    """--maf: one MAF block (formats.maf_lines) per row of the TAB, in the TAB's order; with --strictSelf the rows of the
+    same-scaffold TAB follow those of the main one, as in write_paf.  blocks: the TAB blocks of align_blocks; kept_paths: its
+    (records, first, blocks) of the rows kept.  The text comes from the engine (engine.path_text, kernel K11) in runs of at most
+    `budget` columns; the bytes written do not depend on the budget."""
+    QG = B if B is not None else A
+    with open(path, 'w') as f:
+        f.write(formats.MAF_HEADER + '\n')
+        for _, _, recs, first, blk, row_first, trow, qrow in path_text_runs(A, B, kept_paths, file_order(pairs, blocks, splitSelf), budget):
+            for block in formats.maf_lines(recs, row_first, trow, qrow, first, blk, A.names, A.lengths, QG.names, QG.lengths):
+                f.write(block + '\n')
 
 
 def write_tab(path, pairs, blocks, select=None):
@@ -177,7 +251,8 @@ def region_stat_block(A, B, kept_paths, select, regions, prefix, header):
 
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
-                 B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None):
+                 B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None, maf=None, cs=False,
+                 text_budget=TEXT_BUDGET):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
@@ -186,19 +261,26 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     region_stats: also write, to this file, one line per GFF3 row with the column statistics of the alignment rows that overlap
     the region, clipped to it (--regionStats; formats.region_stat_lines, kernel K10).  The alignment call then asks for the
     paths, with or without paf; rank 0 holds the gathered paths and every rank the genomes, so no collective is added.  Nothing
-    is written when the TAB is recycled (there are no paths)."""
+    is written when the TAB is recycled (there are no paths).  maf: also write the rows of the TAB as MAF to this file (--maf;
+    write_maf); cs: with paf, every PAF row also carries cs:Z: (--cs).  Both take the alignments' text from the engine (kernel
+    K11) on rank 0, in runs of at most text_budget columns; like region_stats they ask the alignment call for the paths and add
+    no collective, and nothing is written when the TAB is recycled."""
     dist = dist or Dist()
+    cs = cs and paf is not None
     kept_paths = None
     outtab_intra = outtab + '_intra.tab'
     kept = None
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
-        blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None or region_stats is not None,
+        blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist,
+                                               paths=paf is not None or region_stats is not None or maf is not None,
                                                divergence=divergence and paf is not None, paf_rows=paf is not None)
         if region_stats is not None:
             kept_paths = more[1]
         if paf is not None and dist.rank == 0:
-            write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None)
+            write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None, cs=(A, B, more[1], blocks, text_budget) if cs else None)
+        if maf is not None and dist.rank == 0:
+            write_maf(maf, A, B, pairs, blocks, more[1], splitSelf=splitSelf and B is None, budget=text_budget)
         if len(set(pairs)) != len(pairs):
             kept = None   # a pair listed twice is written twice (the reference would run it twice): read the file back instead
             kept_paths = None
@@ -208,6 +290,8 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
                 write_tab(outtab_intra, pairs, blocks, select=lambda pr: pr[0] == pr[1])
             else:
                 write_tab(outtab, pairs, blocks)
+    elif maf is not None and dist.rank == 0:
+        logging.warning('--maf needs the alignments\' paths: none with a recycled alignment file; %s is not written', maf)
     if dist.rank != 0:
         return None
     k_main = k_intra = None
@@ -247,18 +331,22 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
 
 
 def map_hits(A, B, pairs, outtab, minIdt=95, minLen=100, hspthresh=3000, reuseTab=False, dist=None, anchor_rule='box',
-             bound_extensions=False, paf=None, divergence=False):
+             bound_extensions=False, paf=None, divergence=False, maf=None, cs=False, text_budget=TEXT_BUDGET):
     """`mimeo map` alignment stage (wrappers.py:525-680): TAB only, no coverage collapse.  anchor_rule, bound_extensions,
-    paf and divergence as self_repeats."""
+    paf, divergence, maf, cs and text_budget as self_repeats."""
     dist = dist or Dist()
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
-        blocks, _, _, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None,
-                                            divergence=divergence and paf is not None)
+        blocks, _, _, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist, paths=paf is not None or maf is not None,
+                                            divergence=divergence and paf is not None, paf_rows=paf is not None)
         if dist.rank == 0:
             write_tab(outtab, pairs, blocks)
             if paf is not None:
-                write_paf(paf, pairs, more[0])
+                write_paf(paf, pairs, more[0], cs=(A, B, more[1], blocks, text_budget) if cs else None)
+            if maf is not None:
+                write_maf(maf, A, B, pairs, blocks, more[1], budget=text_budget)
+    elif maf is not None and dist.rank == 0:
+        logging.warning('--maf needs the alignments\' paths: none with a recycled alignment file; %s is not written', maf)
 
 
 def trf_filter(rows, A, prefix=None, tmatch=2, tmismatch=7, tminscore=50, tmaxperiod=50, maxtandem=40, tdelta=7):
