@@ -116,12 +116,25 @@ __device__ __forceinline__ Base1 base_at(const GStrandView &v, int32_t s) {
 
 // HOXD70 + N = -100 (lastz fill_score) from the difference planes: dl/dh = xor of the lo/hi
 // planes, cg = target base is C or G, nn = either base is N.
+constexpr uint32_t SUB_DL1 = 0x83858E8Eu, SUB_DL0 = 0xE1E1645Bu;  // {-114,-114,-123,-125} : {91,100,-31,-31}, one byte per (dh, cg)
+constexpr int32_t SUB_N = -100;
 __device__ __forceinline__ int32_t sub_score(uint32_t dl, uint32_t dh, uint32_t cg, uint32_t nn) {
-    uint32_t tb = dl ? 0x83858E8Eu : 0xE1E1645Bu;  // {-114,-114,-123,-125} : {91,100,-31,-31}
+    uint32_t tb = dl ? SUB_DL1 : SUB_DL0;
     uint32_t sh = 24u - (((dh << 1) | cg) << 3);
     int32_t s = ((int32_t)(tb << sh)) >> 24;
-    return nn ? -100 : s;
+    return nn ? SUB_N : s;
 }
+// the largest and the smallest score a column can have: what sub_score can return, from its own tables
+constexpr int32_t sub_extreme(bool largest) {
+    int32_t e = SUB_N;
+    for (int k = 0; k < 8; k++) {
+        const int32_t b = (int32_t)(((k < 4 ? SUB_DL0 : SUB_DL1) >> (8 * (k & 3))) & 0xFFu), s = b >= 128 ? b - 256 : b;
+        e = largest ? (s > e ? s : e) : (s < e ? s : e);
+    }
+    return e;
+}
+constexpr int32_t SUB_MAX = sub_extreme(true), SUB_MIN = sub_extreme(false);
+static_assert(SUB_MAX == 100 && SUB_MIN == -125, "HOXD70");
 
 // substitution score and match flag of target base pt against query base pq
 __device__ __forceinline__ int32_t pair_score(const GStrandView &T, const GStrandView &Q, int32_t pt, int32_t pq,

@@ -49,7 +49,8 @@ struct ExtQueues {
     Cand *cand;
     uint64_t *fkey;
     uint32_t *fprev;
-    uint2 *medq, *longq;      // hits whose walk outlives the frame / LONG_WINDOWS windows
+    uint4 *medq;              // hits whose walk outlives the frame: (tpos, qpos, the walk's state at the frame's edge: pack_resume)
+    uint2 *longq;             // hits whose walk outlives LONG_WINDOWS windows
     uint32_t *medu, *longu;   // ... and their units
     uint2 *walkq;             // hits that the filters of K34 could not dismiss (x: tpos, WALK_SHARP_DONE in bit 31; y: qpos): a region of eight shards per unit (FusedUnit)
     unsigned long long *nwalk_u;    // ... entries per unit and shard (workgroup number mod 8, i.e. per XCD)
@@ -237,6 +238,40 @@ __device__ __forceinline__ void walk_window_pred(const uint32_t *__restrict__ ta
     }
 }
 
+// ---- the hand-over of a walk that outlives its frame ---------------------------------------------------------
+// walk_hit serves FRAME_STEPS steps per direction from its frame.  A walk that is alive behind them goes on in
+// k4_extend_generic from the state it has reached, not from the seed: the record carries the state.  Two kinds:
+//   left alive  (kind 0): the left walk's run / best / bk after FRAME_STEPS steps; the right walk has not begun;
+//   right alive (kind 1): the left walk is finished (no earlier seed hit: best / bk final), the right walk's
+//                         run / best / bk after FRAME_STEPS steps.
+// Ranges, whatever the x-drop: a column scores SUB_MIN .. SUB_MAX (sub_score's tables), so after n <= FRAME_STEPS
+// steps  n SUB_MIN <= run <= n SUB_MAX,  0 <= best <= n SUB_MAX  (best starts at 0 and is a prefix sum) and bk <= n:
+// run in 14 bits two's complement, best in 13, bk in 7.
+//   x: run (0..13) | best (14..26) | kind (31)       y: bk (0..6) | finished left bk (7..13) | finished left best (14..26)
+constexpr uint32_t FRAME_STEPS = 64;
+static_assert(-(int32_t)FRAME_STEPS * SUB_MIN < (1 << 13) && (int32_t)FRAME_STEPS * SUB_MAX < (1 << 13), "run: 14 bits signed, best: 13 bits");
+static_assert(FRAME_STEPS < (1u << 7), "bk: 7 bits");
+struct Resume {
+    uint32_t kind;            // 0 left alive, 1 right alive
+    int32_t run, best;        // the walk that is alive, after FRAME_STEPS steps
+    uint32_t bk;
+    int32_t lbest;            // kind 1: the finished left walk
+    uint32_t lbk;
+};
+__device__ __forceinline__ uint2 pack_resume(uint32_t kind, int32_t run, int32_t best, uint32_t bk, int32_t lbest, uint32_t lbk) {
+    return make_uint2(((uint32_t)run & 0x3FFFu) | ((uint32_t)best << 14) | (kind << 31), bk | (lbk << 7) | ((uint32_t)lbest << 14));
+}
+__device__ __forceinline__ Resume unpack_resume(uint32_t x, uint32_t y) {
+    Resume r;
+    r.kind = x >> 31;
+    r.run = ((int32_t)(x << 18)) >> 18;
+    r.best = (int32_t)((x >> 14) & 0x1FFFu);
+    r.bk = y & 0x7Fu;
+    r.lbk = (y >> 7) & 0x7Fu;
+    r.lbest = (int32_t)((y >> 14) & 0x1FFFu);
+    return r;
+}
+
 // entry idx of the group table for G columns per group, computed on the device (the fused kernel builds the
 // 64-entry table of G = 2 in LDS): score sum S, best prefix M and where, lowest prefix mn, packed as above
 template <int G>
@@ -257,8 +292,8 @@ __device__ __forceinline__ uint32_t group_table_entry(uint32_t idx) {
 // seven of the query (13 16-byte loads issued back to back, 2-3 cache lines per sequence), shifts
 // the query into the target's bit frame once, and serves two left windows (64 bases) and two
 // right windows (64 bases) from registers with compile-time word indices.  A walk that is still
-// alive beyond that goes to the generic kernel through a queue (a few per cent of random hits,
-// plus hits inside real similarity).
+// alive beyond that goes to the generic kernel through a queue, with the state it has reached
+// (pack_resume; a few per cent of random hits, plus hits inside real similarity).
 __device__ __forceinline__ uint32_t ext32(uint32_t a, uint32_t b, uint32_t c, uint32_t sh) {
     return sh < 32 ? __builtin_amdgcn_alignbit(b, a, sh) : __builtin_amdgcn_alignbit(c, b, sh - 32);
 }
@@ -469,7 +504,7 @@ __device__ __forceinline__ bool hit_needs_walk(const GStrandView &T, const GStra
 template <int VARIANT>
 __device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const GStrandView &T, const GStrandView &Q,
                                          const uint2 h, int xdrop, int hspthresh, int transitions, bool &q_med,
-                                         bool &q_fol, bool &q_cd, uint64_t &r_fk, uint32_t &r_fp, Cand &r_cd) {
+                                         uint2 &r_st, bool &q_fol, bool &q_cd, uint64_t &r_fk, uint32_t &r_fp, Cand &r_cd) {
     const int32_t et = (int32_t)h.x + SEED_LEN, eq = (int32_t)h.y + SEED_LEN;
     const int32_t d = (int32_t)h.x - (int32_t)h.y;
     const uint32_t bt = h.x & 31u;
@@ -506,8 +541,10 @@ __device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const
     const uint32_t maxl = (uint32_t)min(et, eq);
     left_window<0>(tab, F, bt, transitions, L, maxl, xdrop);
     if (!L.done) left_window<1>(tab, F, bt, transitions, L, maxl, xdrop);
-    if (!L.done) {  // still alive after 64 bases: generic kernel
+    if (!L.done) {  // still alive after 64 bases: generic kernel, from this state on
+        if (L.k != FRAME_STEPS) __builtin_trap();  // a window that does not finish the walk advances it by 32 steps (walk_window_pred)
         q_med = true;
+        r_st = pack_resume(0u, L.run, L.best, L.bk, 0, 0u);
     } else if (L.found) {
         q_fol = true;
         r_fk = ((uint64_t)(uint32_t)(d + (int32_t)Q.len) << 32) | (uint32_t)et;  // the batch key is composed when the record is flushed
@@ -528,7 +565,9 @@ __device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const
             walk_window_pred(tab, R, ext32(F.dl[3], F.dl[4], F.dl[5], rs), ext32(F.dh[3], F.dh[4], F.dh[5], rs),
                              ext32(F.cg[3], F.cg[4], F.cg[5], rs), ext32(F.nn[3], F.nn[4], F.nn[5], rs), 0u, maxr, xdrop);
         if (!R.done) {
+            if (R.k != FRAME_STEPS) __builtin_trap();
             q_med = true;
+            r_st = pack_resume(1u, R.run, R.best, R.bk, L.best, L.bk);
         } else if (L.best + R.best >= hspthresh) {
             q_cd = true;
             r_cd = Cand{(uint32_t)et - L.bk, (uint32_t)eq - L.bk, L.bk + R.bk, L.best + R.best, 0u};
@@ -543,22 +582,25 @@ __device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const
 // registers of the caller.  A queue is flushed when the new records would not fit (a batch adds at most 64); `final`
 // flushes what is left.  Follower records are
 // staged as (diagonal + Q.len) << 32 | seed end and get their batch key (unit, bit widths) at the flush.
+// A generic-walk record is 16 bytes (hit and walk state, pack_resume): s_med has MCAP entries of its own, so that
+// the array costs what CAP 8-byte hits did.
 struct WaveFill { uint32_t n_med, n_fol, n_cd; };
 
 __device__ __forceinline__ uint64_t batch_key(const ExtQueues &q, uint32_t unit, uint64_t staged) {
     return ((uint64_t)unit << (q.dbits + q.ebits)) | ((staged >> 32) << q.ebits) | (staged & 0xFFFFFFFFull);
 }
 
-template <bool STAGE_CAND, int CAP = QCAP>
-__device__ __forceinline__ void stage_records(const ExtQueues &q, uint32_t unit, uint2 *s_med, uint64_t *s_fk, uint32_t *s_fp,
-                                              Cand *s_cd, WaveFill &f, bool q_med, uint2 h, bool q_fol, uint64_t r_fk,
+template <bool STAGE_CAND, int CAP = QCAP, int MCAP = CAP>
+__device__ __forceinline__ void stage_records(const ExtQueues &q, uint32_t unit, uint4 *s_med, uint64_t *s_fk, uint32_t *s_fp,
+                                              Cand *s_cd, WaveFill &f, bool q_med, uint2 h, uint2 r_st, bool q_fol, uint64_t r_fk,
                                               uint32_t r_fp, bool q_cd, Cand r_cd, bool final) {
+    static_assert(MCAP >= 64 && CAP >= 64, "a batch adds up to 64 records of a kind");
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     uint64_t m = __ballot(q_med);
     if (m || (final && f.n_med)) {
         const uint32_t add = (uint32_t)__popcll(m);
-        if (f.n_med + add > (uint32_t)CAP || (final && !m)) {
+        if (f.n_med + add > (uint32_t)MCAP || (final && !m)) {
             __builtin_amdgcn_wave_barrier();  // LDS accesses of one wavefront execute in order
             unsigned long long b = 0;
             if (lane == 0) b = atomicAdd(&q.ctr->nmed8[queue_shard()], (unsigned long long)f.n_med);
@@ -568,7 +610,7 @@ __device__ __forceinline__ void stage_records(const ExtQueues &q, uint32_t unit,
             f.n_med = 0;
             __builtin_amdgcn_wave_barrier();
         }
-        if (q_med) s_med[f.n_med + __popcll(m & lt_mask)] = h;
+        if (q_med) s_med[f.n_med + __popcll(m & lt_mask)] = make_uint4(h.x, h.y, r_st.x, r_st.y);
         f.n_med += add;
         if (final && f.n_med) {
             __builtin_amdgcn_wave_barrier();

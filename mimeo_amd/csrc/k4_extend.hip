@@ -99,16 +99,22 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_extend_generic(const UnitDesc 
 #pragma unroll
             for (int k = 0; k < 7; k++) r += gid >= sh_end[k] ? 1u : 0u;
             const uint64_t at = (uint64_t)r * q.med_cap + (gid - (r ? sh_end[r - 1] : 0));
-            h = q.medq[at];
+            const uint4 rec = q.medq[at];
+            h = make_uint2(rec.x, rec.y);
             unit = q.medu[at];
+            const Resume rs = unpack_resume(rec.z, rec.w);
             const GStrandView T = units[unit].T, Q = units[unit].Q;
             const int32_t et = (int32_t)h.x + SEED_LEN, eq = (int32_t)h.y + SEED_LEN;
             const int32_t d = (int32_t)h.x - (int32_t)h.y;
-            // ---- left walk, with detection of an earlier seed hit at every reached boundary
-            WalkState L{0, 0, 0, 0, false, false, 0};
+            // The walk kernel has served FRAME_STEPS steps of the walk that is alive (two windows): both walks go on from
+            // what it reached, at window RESUME_WIN.  LONG_WINDOWS counts from the seed as before.
+            constexpr int RESUME_WIN = (int)(FRAME_STEPS / 32);
+            // ---- left walk, with detection of an earlier seed hit at every reached boundary (right alive: it is
+            // finished, best and bk are in the record)
+            WalkState L{rs.kind ? 0 : rs.run, rs.kind ? rs.lbest : rs.best, rs.kind ? rs.lbk : rs.bk, rs.kind ? 0u : FRAME_STEPS, rs.kind != 0, false, 0};
             const uint32_t maxl = (uint32_t)min(et, eq);
             bool is_long = false;
-            for (int win = 0; !L.done; win++) {
+            for (int win = RESUME_WIN; !L.done; win++) {
                 if (win == LONG_WINDOWS) { is_long = true; break; }
                 const int32_t P = et - 32 * (win + 1) - SEED_LEN, Pq = P - d;
                 const Win64 tw = win64(T, P), qw = win64(Q, Pq);
@@ -138,11 +144,11 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_extend_generic(const UnitDesc 
                 r_fk = follow_key(q, unit, d, Q.len, (uint32_t)et);
                 r_fp = (uint32_t)et - L.found_step;  // position of the base just summed = that seed's end
             } else {
-                // ---- right walk
-                WalkState R{0, 0, 0, 0, false, false, 0};
+                // ---- right walk: from the seed end, or (right alive) from the record
+                WalkState R{rs.kind ? rs.run : 0, rs.kind ? rs.best : 0, rs.kind ? rs.bk : 0u, rs.kind ? FRAME_STEPS : 0u, false, false, 0};
                 if (!is_long) {
                     const uint32_t maxr = min(T.len - (uint32_t)et, Q.len - (uint32_t)eq);
-                    for (int win = 0; !R.done; win++) {
+                    for (int win = rs.kind ? RESUME_WIN : 0; !R.done; win++) {
                         if (win == LONG_WINDOWS) { is_long = true; break; }
                         const int32_t P = et + 32 * win, Pq = P - d;
                         const Win32 tw = win32(T, P), qw = win32(Q, Pq);
@@ -195,7 +201,8 @@ __device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GSt
                                                  const uint32_t *__restrict__ group_tab, const ExtQueues &q, uint32_t unit,
                                                  int skip_diag0, const unsigned long long *__restrict__ nhits_dev) {
     constexpr bool FILTER = VARIANT == 5 || VARIANT == 9;
-    constexpr int SCAP = 256;   // staged generic-walk hits / followers per wavefront: one same-address atomic per 256 records
+    constexpr int SCAP = 256;   // staged followers per wavefront: one same-address atomic per 256 records
+    constexpr int MCAP = 128;   // ... and generic-walk records, 16 bytes each with the walk's state: the 16 KiB that 256 bare hits took
     // nhits_dev: the hits are the walk queue of this unit, filled by K34 just before on the same stream: eight shards of
     // capacity `nhits` each, the counts on the device.  sh_end[r] = hits in shards 0 .. r.
     uint64_t sh_end[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -207,7 +214,7 @@ __device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GSt
         nhits = acc;
     }
     __shared__ uint32_t tab[GROUP_TAB];
-    __shared__ uint2 s_med[FAST_THREADS / 64][SCAP];
+    __shared__ uint4 s_med[FAST_THREADS / 64][MCAP];
     __shared__ uint64_t s_fk[FAST_THREADS / 64][SCAP];
     __shared__ uint32_t s_fp[FAST_THREADS / 64][SCAP];
     __shared__ Cand s_cd[FAST_THREADS / 64][QCAP];
@@ -224,8 +231,9 @@ __device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GSt
         uint64_t r_fk = 0;
         uint32_t r_fp = 0;
         Cand r_cd{0, 0, 0, 0, 0};
-        if (active) walk_hit<1>(tab, T, Q, h, xdrop, hspthresh, transitions, q_med, q_fol, q_cd, r_fk, r_fp, r_cd);
-        stage_records<true, SCAP>(q, unit, s_med[wv], s_fk[wv], s_fp[wv], s_cd[wv], fill, q_med, h, q_fol, r_fk, r_fp, q_cd, r_cd, final);
+        uint2 r_st = make_uint2(0, 0);
+        if (active) walk_hit<1>(tab, T, Q, h, xdrop, hspthresh, transitions, q_med, r_st, q_fol, q_cd, r_fk, r_fp, r_cd);
+        stage_records<true, SCAP, MCAP>(q, unit, s_med[wv], s_fk[wv], s_fp[wv], s_cd[wv], fill, q_med, h, r_st, q_fol, r_fk, r_fp, q_cd, r_cd, final);
     };
 
     const uint64_t stride = (uint64_t)gridDim.x * FAST_THREADS;
@@ -774,6 +782,25 @@ const uint32_t *group_table_device() {
     return g_group_tab;
 }
 
+// k4_extend_generic strides over its queue with every wavefront the device can hold at once: workgroups per CU as the
+// runtime counts them for this kernel's registers and LDS (five on gfx950: 83 VGPRs, 27 KiB) times the CUs
+static uint32_t g_generic_grid = 0;
+static std::once_flag g_generic_once;
+static uint32_t generic_grid() {
+    std::call_once(g_generic_once, [&] {
+        int dev = 0, cus = 0, per_cu = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k4_extend_generic, EXT_THREADS, 0) == hipSuccess && cus > 0 && per_cu > 0)
+            g_generic_grid = (uint32_t)cus * (uint32_t)per_cu;
+        else {
+            g_generic_grid = 1024;   // what the kernel ran with before it was sized: four wavefronts per SIMD of 256 CUs
+            (void)hipGetLastError();
+        }
+        if (getenv("MIMEO_K4_STATS")) fprintf(stderr, "[k4] k4_extend_generic: %u workgroups (%d CUs x %d)\n", g_generic_grid, cus, per_cu);
+    });
+    return g_generic_grid;
+}
+
 // fused heavy kernel (k34_fused.hip)
 int launch_fused_batch(const FusedUnit *d_units, uint32_t nactive, const ExtQueues &q, const HeavyPlan &plan, const mimeo_params *p, hipStream_t st,
                        uint32_t dbg);
@@ -816,12 +843,12 @@ int ExtBatch::run(const std::vector<UnitWork> &work, const mimeo_params *p, uint
 }
 
 // Device bytes of the batch's queues at the current capacities: followers and walks beyond the frame in eight shards (key +
-// predecessor / hit + unit), long walks, candidates + HSPs (+ their mirror copies), the walk queue of one unit.  The
+// predecessor: 12 bytes / hit + walk state + unit: 20 bytes), long walks, candidates + HSPs (+ their mirror copies), the walk queue of one unit.  The
 // follower sort's second buffer, flags, segment lists and rocPRIM's scratch are sized by the followers actually seen
 // (finish()): up to 41 bytes each on top.
 uint64_t ExtBatch::arena_bytes() const {   // the queues proper: what the first arena holds
     const uint64_t mf = mirror_dst_.empty() ? 1 : 2;
-    return cap_f_ * 8 * 12 + cap_m_ * 8 * 12 + cap_l_ * 12 + cap_c_ * (sizeof(Cand) + mf * (sizeof(mimeo_hsp) + 4)) + (v1_ ? 8 : walk_entries_ * 8) + 4096;
+    return cap_f_ * 8 * 12 + cap_m_ * 8 * 20 + cap_l_ * 12 + cap_c_ * (sizeof(Cand) + mf * (sizeof(mimeo_hsp) + 4)) + (v1_ ? 8 : walk_entries_ * 8) + 4096;
 }
 // ... plus what the rest of the batch may ask for while they are alive: the follower sort's second arena at its worst (every
 // shard full: 41 bytes per follower) and the chain / gapped stage's scratch and alignment slots (~200 bytes per HSP, 60 more
@@ -972,7 +999,7 @@ int ExtBatch::enqueue_heavy() {
     {
         {   // the queues of the batch: slices of one allocation (it grows when a batch needs more, with room to spare, and stays)
             const size_t mf = mirror_dst_.empty() ? 1 : 2;
-            const size_t sz[10] = {cap_f * 8 * 8, cap_f * 8 * 4, cap_m * 8 * 8, cap_m * 8 * 4, cap_l * 8, cap_l * 4, cap_c * sizeof(Cand),
+            const size_t sz[10] = {cap_f * 8 * 8, cap_f * 8 * 4, cap_m * 8 * 16, cap_m * 8 * 4, cap_l * 8, cap_l * 4, cap_c * sizeof(Cand),
                                    cap_c * sizeof(mimeo_hsp) * mf, cap_c * 4 * mf, v1 ? 8 : walk_entries_ * 8 + 8};
             size_t total = 0;
             for (size_t z : sz) total += (z + 255) & ~(size_t)255;
@@ -995,7 +1022,7 @@ int ExtBatch::enqueue_heavy() {
         }
         q.ctr = (ExtCounters *)ctr.p;
         q.cand = (Cand *)cand.p; q.fkey = (uint64_t *)fkey.p; q.fprev = (uint32_t *)fprev.p;
-        q.medq = (uint2 *)medq.p; q.medu = (uint32_t *)medu.p; q.longq = (uint2 *)longq.p; q.longu = (uint32_t *)longu.p;
+        q.medq = (uint4 *)medq.p; q.medu = (uint32_t *)medu.p; q.longq = (uint2 *)longq.p; q.longu = (uint32_t *)longu.p;
         q.bigcand = (unsigned long long *)bigcand.p; q.bigacc = (unsigned long long *)bigacc.p;
         q.unit_hits = (unsigned long long *)unit_hits.p;
         q.tile_hits = (unsigned long long *)tile_hits.p;
@@ -1129,7 +1156,7 @@ int ExtBatch::finish(uint64_t *nhsp_out, ExtStats *stats) {
         HIP_TRY(hipStreamWaitEvent(st, ev[1], 0));   // the heavy phase may have run on another stream
         // ---- tails, once per batch
         HIP_TRY(hipEventRecord(ev[3], st));
-        hipLaunchKernelGGL(k4_extend_generic, dim3(1024), dim3(EXT_THREADS), 0, st, d_units, q, p->xdrop, p->hspthresh,
+        hipLaunchKernelGGL(k4_extend_generic, dim3(generic_grid()), dim3(EXT_THREADS), 0, st, d_units, q, p->xdrop, p->hspthresh,
                            p->transitions, tab);
         if (!h_selfs.empty()) HIP_TRY(hipStreamWaitEvent(st, side_done, 0));
         hipLaunchKernelGGL(k4_extend_long, dim3(768), dim3(EXT_THREADS), 0, st, d_units, q, p->xdrop, p->hspthresh, p->transitions);
