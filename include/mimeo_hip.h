@@ -287,6 +287,13 @@ int mimeo_align_pairs(const mimeo_genome *A, const mimeo_genome *B, const uint32
  * (mimeo_amd/dist.py deal_units): all minus-strand units of its target rows, and the plus-strand units
  * of the unordered scaffold pairs dealt to it in BOTH orders, so that the shared plus strand applies.
  * Results are concatenated in pair order, a pair's plus-strand rows first.
+ *
+ * What is left out at a limit (mimeo_align_pairs) is a SCAFFOLD pair, not an entry of the list: when a group of (t, q)
+ * hits a limit on either strand, every entry k of the call with (pair_t[k], pair_q[k]) == (t, q) yields no row and no
+ * path block, whatever strands it names, and mimeo_get_failed_pairs reports each such entry once — a duplicate of the
+ * pair, and the entry that carries the pair's other strand, included.  The set of failed scaffold pairs depends neither
+ * on how the call is worked off nor on the entry point.  (Across calls nothing is known: a caller that spreads a pair's
+ * strands over calls or ranks drops the pair itself — workflow.drop_failed_pairs.)
  */
 int mimeo_align_units(const mimeo_genome *A, const mimeo_genome *B, const uint32_t *pair_t,
                       const uint32_t *pair_q, const uint8_t *pair_strand, uint64_t npairs,
@@ -451,7 +458,10 @@ int mimeo_path_text(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, 
 /*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
- * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  mimeo_last_error() describes the last one.
+ * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  A left-out pair is a scaffold pair: EVERY entry of the
+ * list that names it is reported, once each, in no particular order — also a duplicate and an entry that asked for
+ * the other strand only (mimeo_align_units).  mimeo_last_error() describes one of the groups that hit the limit,
+ * with its strand ('+' or '-').
  */
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n);
 

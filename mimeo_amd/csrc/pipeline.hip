@@ -481,9 +481,9 @@ static int run_packed(const mimeo_genome *A, const mimeo_genome *QG, const uint3
         Group last;
         HIP_TRY(hipMemcpy(&last, (const Group *)g_groups.p + (ngroups - 1), sizeof(Group), hipMemcpyDeviceToHost));
         if (sum[1]) {   // a pair that hit a limit is left out; the others go on (the reference's script has no `set -e`: utils.py:125-128)
-            std::vector<uint2> bad;
+            std::vector<uint3> bad;
             if ((rc = overflowed_groups_device((const Group *)g_groups.p, ngroups, sum[1], &bad))) return rc;
-            for (const uint2 &tq : bad) record_failure(pairidx[(size_t)trank[tq.x] * nq + qrank[tq.y]], tq.x, tq.y, '?', failed);
+            for (const uint3 &tq : bad) record_failure(pairidx[(size_t)trank[tq.x] * nq + qrank[tq.y]], tq.x, tq.y, tq.z ? '-' : '+', failed);
         }
         g_stats.chained_hsps += sum[0];
         std::vector<mimeo_alignment> host_aln;
@@ -503,8 +503,7 @@ static int run_packed(const mimeo_genome *A, const mimeo_genome *QG, const uint3
         for (auto &dp : cp.dups) {
             per_pair[dp.first] = per_pair[dp.second];
             if (pp) { pp->cnt[dp.first] = pp->cnt[dp.second]; pp->blk[dp.first] = pp->blk[dp.second]; }
-            if (failed[dp.second]) failed[dp.first] = 1;
-        }
+        }   // a failed pair's duplicates are failed with it by align_units_impl
     return rc;
 }
 
@@ -624,6 +623,18 @@ int align_units_impl(const mimeo_genome *A, const mimeo_genome *B, const uint32_
         if (ps.strand && (rc = run_packed(A, QG, pair_t, pair_q, npairs, &ps, sw, per_pair, failed, pp, tm, &packed))) return rc;
     }
     if (!packed && (rc = run_per_pair(A, QG, pair_t, pair_q, strands, p, sw, per_pair, failed, pp, tm))) return rc;
+    // What is left out is a SCAFFOLD pair: every entry of the list that names the (t, q) of a failed entry fails with it — a
+    // duplicate, or the entry that carries the pair's other strand (dist.units_of_row) — and is reported once.
+    if (!g_failed.empty()) {
+        std::set<std::pair<uint32_t, uint32_t>> bad;
+        for (uint64_t k = 0; k < npairs; k++)
+            if (failed[k]) bad.emplace(pair_t[k], pair_q[k]);
+        for (uint64_t k = 0; k < npairs; k++)
+            if (!failed[k] && bad.count(std::make_pair(pair_t[k], pair_q[k]))) {
+                failed[k] = 1;
+                g_failed.emplace_back(k, MIMEO_ERR_LIMIT);
+            }
+    }
     for (uint64_t k = 0; k < npairs; k++)
         if (failed[k]) {   // a pair that hit a limit on one strand yields no rows at all (its lastz run failed)
             per_pair[k].clear();

@@ -95,12 +95,14 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, 
         mine = list(pairs)
         alns = run(engine.align_pairs, mine)
         failed = [mine[i] for i, _ in engine.failed_pairs()] if mine else []
-    for t, q in failed:   # the reference's script loses a failing lastz run's rows and goes on (utils.py:125-128)
-        logging.warning('Alignment of %s onto %s hit an engine limit and was left out: %s', QG.names[q], A.names[t], engine.last_error())
     if paths:
         alns, first, blk = alns
         first, blk = dist.allgather_paths(first, blk)
     alns = dist.allgather_records(alns)
+    alns, first, blk, left_out = drop_failed_pairs(dist, alns, first, blk, failed)
+    for t, q in (left_out if dist.rank == 0 else ()):   # the reference's script loses a failing lastz run's rows and goes on (utils.py:125-128)
+        logging.warning('Alignment of %s onto %s hit an engine limit and was left out (a DP band wider than 65536 columns, or a '
+                        'traceback larger than the trace pool)', QG.names[q], A.names[t])
     if not paths:
         blocks, kept = formats.tab_blocks(alns, A.names, QG.names, min_len, min_idt)
         return blocks, int(alns.size), kept
@@ -116,6 +118,23 @@ def align_blocks(A, B, pairs, params, min_len, min_idt, dist=None, paths=False, 
         paf_blocks[pr] = paf[at:at + len(blocks[pr])]
         at += len(blocks[pr])
     return blocks, int(alns.size), kept, paf_blocks, (alns[rows[0]], f2, b2)
+
+
+def drop_failed_pairs(dist, alns, first, blk, failed):
+    """What is left out of a job is a scaffold pair (mimeo_hip.h, mimeo_get_failed_pairs), on every rank: `failed`, this
+    rank's (t, q) that hit an engine limit, are exchanged (one all-gatherv, which every rank joins — a rank without work or
+    without failures too), and every record of a pair of the union goes, with its path: the other strand of a pair whose
+    strands dist.deal_units dealt to two ranks was computed by a rank that saw nothing fail.  alns (and first / blk, or None
+    without paths): the gathered records.  Returns (alns, first, blk, the sorted union); the order of the rest is kept."""
+    mine = np.array(sorted(set((int(t), int(q)) for t, q in failed)), dtype=np.uint32).reshape(-1, 2)
+    union = sorted(set(map(tuple, dist.allgather_records(mine).reshape(-1, 2).tolist())))
+    if union and alns.size:
+        key = alns['tid'].astype(np.uint64) << np.uint64(32) | alns['qid'].astype(np.uint64)
+        keep = np.flatnonzero(~np.isin(key, np.array([t << 32 | q for t, q in union], dtype=np.uint64)))
+        if first is not None:
+            first, blk = formats.select_paths(first, blk, keep)
+        alns = alns[keep]
+    return alns, first, blk, union
 
 
 TEXT_BUDGET = 1 << 26   # columns of alignment text asked of the engine at once by the writers: two rows of 64 MiB
