@@ -456,6 +456,51 @@ int mimeo_path_text(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, 
                     uint64_t **row_first /* n + 1 */, uint8_t **trow, uint8_t **qrow /* row_first[n] bytes each */);
 
 /*
+ * Repeat families: the regions of a self job linked through the alignment paths (kernel K12) — which repeats are copies of
+ * each other.  Replaces nothing in the reference, which keeps lastz's coordinates and no alignment.  An alignment row that
+ * covers a region of its target scaffold is projected, through its path, onto its query scaffold; a region that the projection
+ * covers belongs to the same family.  The join of rows and regions has one item per pair: a family of c copies makes on the
+ * order of c * c of them, so the rule runs on the device, with a lock-free union-find over the regions.
+ *
+ * "Family linking v1".  Inputs:
+ *   T, aln, n, path_first, blocks, nblocks   as for mimeo_path_stats; a self job: the query scaffolds are T's
+ *   regions[0 .. nreg)       sorted by (chrom, start) and disjoint, none empty — as mimeo_coverage_collapse returns them
+ *   chrom_of_scaf[nscaf]     the region chromosome number of scaffold i; NULL: i itself.  It numbers every chromosome once
+ *   items[0 .. nitems)       `aln` a record, `group` the number r of a region of that record's TARGET scaffold, [w0, w1) the
+ *                            part of the region that the record is asked about (the overlap of the two, as a rule)
+ *   min_cover_pct            1 .. 100
+ * Per item, with r = [rs, re):
+ *   A  the alignment covers the region: 100 * (w1 - w0) >= min_cover_pct * (re - rs).  Otherwise the item links nothing.
+ *   B  projection.  Of the columns of the record's blocks, take those whose target base lies in [w0, w1).  None (the window
+ *      lies wholly in a deletion, or off the alignment, or the record has no block): the item links nothing.  Otherwise q_lo
+ *      is the aligned-strand query coordinate (mimeo_path_block.q) of the first such column and q_hi that of the last one
+ *      plus one; on the query's plus strand the projection is P = [q_lo, q_hi) for qstrand 0 and [Lq - q_hi, Lq - q_lo) for
+ *      qstrand 1, Lq the query scaffold's length.
+ *   C  linking.  For every region s = [ss, se) of scaffold qid with ov = |P n s| > 0: if 100 * ov >= min_cover_pct * (se - ss)
+ *      and s != r, then r and s are in one family and links[r] grows by one.  s == r (a tandem array inside one region) is
+ *      skipped and not counted.
+ * All arithmetic is in 64 bits; there are no floats.
+ *
+ * Output (caller's arrays of nreg entries): family[i] is the smallest region number in region i's component of the graph of
+ * these links (family[i] <= i; a region nobody links is its own family), links[i] the number of (item, s) that linked from
+ * region i.  Both depend on nothing but the inputs: not on the order of the items, the grid, or the cut into slices.
+ * nitems == 0: family[i] = i, links[i] = 0, MIMEO_OK, nothing else is looked at.
+ *
+ * Everything is checked before the device sees it; a violation is MIMEO_ERR_ARG with a message that starts with
+ * "mimeo_link_regions:" and names the item, the region, or the record and the block: min_cover_pct in 1 .. 100; everything
+ * mimeo_path_stats checks; chrom_of_scaf[i] < nscaf and no chromosome twice; the regions sorted, disjoint, start < end, and
+ * end inside the scaffold of their chromosome; per item aln < n, group < nreg, the region's chrom == chrom_of_scaf[tid], and
+ * rs <= w0 <= w1 <= re.  Records and blocks go to the device in the same bounded slices as for mimeo_path_stats, and only
+ * the slices that an item asks for; the union-find stays on the device across them.
+ *
+ * A new symbol beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs it checks for the symbol.
+ */
+int mimeo_link_regions(const mimeo_genome *T, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first,
+                       const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_interval *regions, uint64_t nreg,
+                       const uint32_t *chrom_of_scaf /* NULL: identity */, const mimeo_window_item *items, uint64_t nitems,
+                       uint32_t min_cover_pct, uint32_t *family /* caller's, nreg entries */, uint64_t *links /* caller's, nreg entries */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  A left-out pair is a scaffold pair: EVERY entry of the

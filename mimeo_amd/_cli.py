@@ -77,6 +77,29 @@ def add_region_stats(parser):
                              'with --recycle when the alignment file exists.')
 
 
+def add_families(parser):
+    """--families / --familyCover of `mimeo self` (`mimeo x` has its query in another genome)"""
+    parser.add_argument('--families', type=str, default=None, metavar='FILE',
+                        help='Also write one line per feature of the GFF3 to FILE (tab-separated, with a header): its ID, seqid, start and '
+                             'end, the repeat family it belongs to (F1, F2, ... in the order of their first member; with --strictSelf the '
+                             'same-scaffold block follows as F1_intra, ...), the members and summed bases of the family, and how often '
+                             'the feature was linked to another one. Two features are of one family when an alignment row that covers '
+                             '--familyCover per cent of the one lands, through its alignment, on --familyCover per cent of the other; '
+                             'computed on the GPU. Off by default: without it no path is computed. Nothing is written with --recycle when '
+                             'the alignment file exists.')
+    parser.add_argument('--familyCover', type=int, default=80, metavar='PCT',
+                        help='With --families: the share of a feature, in per cent (1..100), that an alignment must cover on both '
+                             'sides to link two features. Default 80, the "80 %% of the length" of the 80-80-80 rule for transposable-'
+                             'element families; identity is governed by --minIdt.')
+
+
+def check_families(parser, args):
+    """--familyCover of `mimeo self` (parser.error exits with status 2, before the engine starts)"""
+    if not 1 <= args.familyCover <= 100:
+        parser.error('--familyCover must be in 1..100')
+    return args
+
+
 def check_common(parser, args):
     """cross-flag rules of add_common (parser.error exits with status 2)"""
     if args.boundExtensions and args.anchorRule != 'path':

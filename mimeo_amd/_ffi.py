@@ -19,7 +19,7 @@ SYMBOLS = [
     'mimeo_coverage_collapse', 'mimeo_tandem_masked', 'mimeo_genome_load_fasta', 'mimeo_genome_name',
     'mimeo_genome_keep_indexes', 'mimeo_genome_drop_indexes', 'mimeo_genome_build_indexes', 'mimeo_coverage_bedgraph',
     'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths', 'mimeo_path_stats',
-    'mimeo_path_window_stats', 'mimeo_path_text',
+    'mimeo_path_window_stats', 'mimeo_path_text', 'mimeo_link_regions',
 ]
 
 
@@ -122,6 +122,8 @@ def load():
         lib.mimeo_path_window_stats.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, u64, vp]
     if hasattr(lib, 'mimeo_path_text'):
         lib.mimeo_path_text.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(lib, 'mimeo_link_regions'):
+        lib.mimeo_link_regions.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

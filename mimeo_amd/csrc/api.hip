@@ -412,6 +412,21 @@ int mimeo_path_text(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_al
     return path_text_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, row_first, trow, qrow);
 }
 
+int mimeo_link_regions(const mimeo_genome *T, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first, const mimeo_path_block *blocks,
+                       uint64_t nblocks, const mimeo_interval *regions, uint64_t nreg, const uint32_t *chrom_of_scaf, const mimeo_window_item *items,
+                       uint64_t nitems, uint32_t min_cover_pct, uint32_t *family, uint64_t *links) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (nreg && (!family || !links)) { set_error("mimeo_link_regions: null argument"); return MIMEO_ERR_ARG; }
+    if (nreg > 0xFFFFFFFFull) { set_error("mimeo_link_regions: more than 2^32 - 1 regions"); return MIMEO_ERR_ARG; }
+    if (!nitems) {   // nothing links anything: every region is its own family
+        for (uint64_t i = 0; i < nreg; i++) { family[i] = (uint32_t)i; links[i] = 0; }
+        return MIMEO_OK;
+    }
+    if (!T || !items || (nreg && !regions) || (n && (!aln || !path_first)) || (nblocks && !blocks)) { set_error("mimeo_link_regions: null argument"); return MIMEO_ERR_ARG; }
+    return link_regions_device(T, aln, n, path_first, blocks, nblocks, regions, nreg, chrom_of_scaf, items, nitems, min_cover_pct, family, links);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

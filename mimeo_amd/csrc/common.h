@@ -345,5 +345,10 @@ int window_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const mime
 // K11: the two rows of every alignment as letters (k11_path_text.hip); host in, three malloc'ed arrays out.  Q is never null here.
 int path_text_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
                      const mimeo_path_block *blocks, uint64_t nblocks, uint64_t **row_first, uint8_t **trow, uint8_t **qrow);
+// K12: regions linked into families through alignment paths (k12_link_regions.hip); host in, host out.  A self job, and
+// nitems > 0.
+int link_regions_device(const mimeo_genome *T, const mimeo_alignment *aln, uint64_t n, const uint64_t *first, const mimeo_path_block *blocks,
+                        uint64_t nblocks, const mimeo_interval *regions, uint64_t nreg, const uint32_t *chrom_of_scaf, const mimeo_window_item *items,
+                        uint64_t nitems, uint32_t min_cover_pct, uint32_t *family, uint64_t *links);
 
 }  // namespace mimeo

@@ -224,6 +224,51 @@ def window_stats(A, B, records, first, blocks, items, ngroups):
     return out
 
 
+def link_regions(A, records, first, blocks, regions, chrom_of_tid, items, min_cover_pct=80):
+    """Repeat families (mimeo_link_regions, kernel K12): (family, links), two arrays with one entry per region — family[i] the
+    smallest region number of the family of region i (uint32; family[i] <= i), links[i] how often region i was linked to
+    another one (uint64).  A self job: records / first / blocks as for path_stats, with the queries scaffolds of A; regions:
+    _ffi.INTERVAL rows as coverage_collapse returns them (or an (n, 3) array), sorted by (chrom, start) and disjoint;
+    chrom_of_tid[tid]: the region chromosome number of scaffold tid (None: tid itself); items: _ffi.WINDOW_ITEM rows (or an
+    (n, 4) array) of (record number, region number, w0, w1) as formats.region_items makes them.  An item whose window covers
+    min_cover_pct per cent of its region is projected through the record's path onto the query scaffold, and every other
+    region of which the projection covers min_cover_pct per cent joins the family (include/mimeo_hip.h has the rule).  A bad
+    path, region or item is a RuntimeError naming it, raised before anything runs on the device."""
+    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
+    if first.size != recs.size + 1:
+        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_link_regions'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_link_regions: rebuild the library')
+    reg = np.asarray(regions)
+    if reg.dtype != _ffi.INTERVAL:
+        a = np.asarray(reg, dtype=np.uint32).reshape(-1, 3)
+        reg = np.zeros(a.shape[0], dtype=_ffi.INTERVAL)
+        reg['chrom'], reg['start'], reg['end'] = a[:, 0], a[:, 1], a[:, 2]
+    reg = np.ascontiguousarray(reg)
+    it = np.asarray(items)
+    if it.dtype != _ffi.WINDOW_ITEM:
+        a = np.asarray(it, dtype=np.uint32).reshape(-1, 4)
+        it = np.zeros(a.shape[0], dtype=_ffi.WINDOW_ITEM)
+        it['aln'], it['group'], it['w0'], it['w1'] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    it = np.ascontiguousarray(it)
+    cot = None
+    if chrom_of_tid is not None:
+        cot = np.ascontiguousarray(chrom_of_tid, dtype=np.uint32)
+        if cot.size != len(A.names):
+            raise ValueError('chrom_of_tid has %d entries for %d scaffolds' % (cot.size, len(A.names)))
+    if not 0 <= int(min_cover_pct) <= 0xFFFFFFFF:
+        raise ValueError('min_cover_pct must be in 1..100, not %r' % (min_cover_pct,))
+    family, links = np.zeros(reg.size, dtype=np.uint32), np.zeros(reg.size, dtype=np.uint64)
+    _ffi.check(lib.mimeo_link_regions(A._h, recs.ctypes.data if recs.size else None, recs.size, first.ctypes.data,
+                                      blk.ctypes.data if blk.size else None, blk.size, reg.ctypes.data if reg.size else None, reg.size,
+                                      cot.ctypes.data if cot is not None else None, it.ctypes.data if it.size else None, it.size,
+                                      int(min_cover_pct), family.ctypes.data if reg.size else None, links.ctypes.data if reg.size else None))
+    return family, links
+
+
 def path_text(A, B, records, first, blocks):
     """The text of alignment paths (mimeo_path_text, kernel K11): (row_first, trow, qrow) as numpy arrays (<u8, uint8, uint8).
     Row i is trow[row_first[i]:row_first[i + 1]] over the same range of qrow: the target's letters over the aligned query

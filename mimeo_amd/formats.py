@@ -433,6 +433,29 @@ def region_stat_lines(regions, names_sorted, prefix, stats, rows, header=True):
     return lines
 
 
+FAMILY_HEADER = '\t'.join(('#ID', 'seqid', 'start', 'end', 'family', 'members', 'family_bases', 'links'))
+
+
+def family_lines(regions, names_sorted, prefix, family, links, suffix='', header=True):
+    """--families: FAMILY_HEADER (header=True), then one tab-separated line per region, in the order of the GFF3 rows.  ID,
+    seqid, start and end are those of the region's GFF3 row (gff_repeat_lines), as in region_stat_lines; family / links: what
+    engine.link_regions returned for the regions.  The families are named F1, F2, ... (+ suffix: the second block of
+    --strictSelf) in the order of their first member, a region that is linked to no other being a family of one; members and
+    family_bases are the number of regions of the family and their summed length; links is the region's own count."""
+    lines = [FAMILY_HEADER] if header else []
+    fam = [int(f) for f in family]
+    name, members, bases = {}, {}, {}
+    for r, f in zip(regions, fam):
+        if f not in name:
+            name[f] = 'F%d%s' % (len(name) + 1, suffix)
+        members[f] = members.get(f, 0) + 1
+        bases[f] = bases.get(f, 0) + int(r['end']) - int(r['start'])
+    for i, (r, f) in enumerate(zip(regions, fam), 1):
+        lines.append('\t'.join(['%s_%05d' % (prefix, i), names_sorted[int(r['chrom'])], str(int(r['start'])), str(int(r['end'])), name[f],
+                                str(members[f]), str(bases[f]), str(int(links[i - 1]))]))
+    return lines
+
+
 def import_align(tab_rows, prefix=None, min_len=100, min_idt=95):
     """wrappers.py:33-117 import_Align: re-filter on int(end)-int(start) and float(pID); sort on
     the STRING columns tName, tStart, tEnd, tStrand (lexicographic, stable); UID = prefix_<rank>

@@ -13,12 +13,13 @@ def mainArgs(argv=None):
     _cli.add_common(parser, 'mimeo-self', 'mimeo-self_repeats.gff3', 'Self_Repeat', 'Self_Repeat', with_b=False)
     parser.add_argument('--bedtools', type=str, default='bedtools', help='Accepted for compatibility; bedtools is not used.')
     _cli.add_region_stats(parser)
+    _cli.add_families(parser)
     parser.add_argument('--minCov', type=int, default=3, help='Minimum depth of aligned segments to report repeat feature.')
     parser.add_argument('--intraCov', type=int, default=5,
                         help='Minimum depth of aligned segments from same scaffold to report feature. Used if "--strictSelf" mode is selected.')
     parser.add_argument('--strictSelf', action='store_true',
                         help='If set process same-scaffold alignments separately with option to use higher "--intraCov" threshold.')
-    return _cli.check_common(parser, parser.parse_args(argv))
+    return _cli.check_families(parser, _cli.check_common(parser, parser.parse_args(argv)))
 
 
 def main(argv=None):
@@ -36,7 +37,7 @@ def main(argv=None):
                           minCov=args.minCov, intraCov=args.intraCov, splitSelf=args.strictSelf, reuseTab=args.recycle,
                           label=args.label, prefix=args.prefix, dist=dist,
                           anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence,
-                          region_stats=args.regionStats, maf=args.maf, cs=args.cs)
+                          region_stats=args.regionStats, maf=args.maf, cs=args.cs, families=args.families, family_cover=args.familyCover)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

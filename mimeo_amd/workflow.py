@@ -268,10 +268,25 @@ def region_stat_block(A, B, kept_paths, select, regions, prefix, header):
     return formats.region_stat_lines(regions, names_sorted, prefix, stats, per_region, header=header)
 
 
+def family_block(A, kept_paths, select, regions, prefix, cover, suffix, header):
+    """--families for one block of GFF3 rows: the rows `select` (a mask) of the kept rows' (records, first, blocks) joined with
+    `regions` (formats.region_items, without the trivial self rows), one engine.link_regions call (kernel K12), the lines of
+    formats.family_lines."""
+    recs, first, blk = kept_paths
+    rows = np.flatnonzero(select)
+    f2, b2 = formats.select_paths(first, blk, rows)
+    names_sorted = sorted(A.names, key=lambda s: s.encode())
+    cid = {n: i for i, n in enumerate(names_sorted)}
+    chrom_of_tid = [cid[n] for n in A.names]
+    items, _ = formats.region_items(recs[rows], regions, chrom_of_tid, first=f2, blocks=b2, self_job=True)
+    family, links = engine.link_regions(A, recs[rows], f2, b2, regions, chrom_of_tid, items, cover)
+    return formats.family_lines(regions, names_sorted, prefix, family, links, suffix=suffix, header=header)
+
+
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
                  B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None, maf=None, cs=False,
-                 text_budget=TEXT_BUDGET):
+                 text_budget=TEXT_BUDGET, families=None, family_cover=80):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
@@ -283,18 +298,27 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     is written when the TAB is recycled (there are no paths).  maf: also write the rows of the TAB as MAF to this file (--maf;
     write_maf); cs: with paf, every PAF row also carries cs:Z: (--cs).  Both take the alignments' text from the engine (kernel
     K11) on rank 0, in runs of at most text_budget columns; like region_stats they ask the alignment call for the paths and add
-    no collective, and nothing is written when the TAB is recycled."""
+    no collective, and nothing is written when the TAB is recycled.  families (`mimeo self` only: ValueError with B): also
+    write, to this file, one line per GFF3 row with the repeat family of the region (--families; formats.family_lines, kernel
+    K12): two regions are of one family when an alignment row that covers family_cover per cent of the one projects, through
+    its path, onto family_cover per cent of the other (include/mimeo_hip.h "family linking v1").  Like region_stats it asks the
+    alignment call for the paths, runs on rank 0 and adds no collective; with splitSelf the intra block is linked on its own
+    and its families are named F1_intra ...; nothing is written when the TAB is recycled or a pair is listed twice."""
     dist = dist or Dist()
     cs = cs and paf is not None
+    if families is not None and B is not None:
+        raise ValueError('families needs a self job: the regions and the queries must lie in one genome')
+    if families is not None and not 1 <= int(family_cover) <= 100:
+        raise ValueError('family_cover must be in 1..100, not %r' % (family_cover,))
     kept_paths = None
     outtab_intra = outtab + '_intra.tab'
     kept = None
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
         blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist,
-                                               paths=paf is not None or region_stats is not None or maf is not None,
+                                               paths=paf is not None or region_stats is not None or maf is not None or families is not None,
                                                divergence=divergence and paf is not None, paf_rows=paf is not None)
-        if region_stats is not None:
+        if region_stats is not None or families is not None:
             kept_paths = more[1]
         if paf is not None and dist.rank == 0:
             write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None, cs=(A, B, more[1], blocks, text_budget) if cs else None)
@@ -345,6 +369,19 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
                 rl += region_stat_block(A, B, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), False)
             with open(region_stats, 'w') as f:
                 for line in rl:
+                    f.write(line + '\n')
+    if families is not None:
+        if kept_paths is None:
+            logging.warning('--families needs the alignments\' paths: none with a recycled alignment file or a pair listed twice; %s is not written',
+                            families)
+        else:
+            none = np.zeros(0, dtype=engine._ffi.INTERVAL)
+            fl = family_block(A, kept_paths, ~intra if splitSelf else np.ones(kept.shape[0], bool), reg_main[0] if reg_main else none, str(prefix),
+                              int(family_cover), '', True)
+            if splitSelf:   # the intra block is linked on its own; its lines follow, with their restarted IDs, as in the GFF3
+                fl += family_block(A, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), int(family_cover), '_intra', False)
+            with open(families, 'w') as f:
+                for line in fl:
                     f.write(line + '\n')
     return lines
 
