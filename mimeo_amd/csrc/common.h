@@ -32,6 +32,7 @@
 
 #include "../../include/mimeo_hip.h"
 #include "host_plan.h"
+#include "queue_plan.h"
 
 namespace mimeo {
 
@@ -195,22 +196,44 @@ struct ExtStats {
 // kernel of round 1 per unit) appending to batch-wide queues, then the tails ONCE per batch: walks beyond the frame,
 // k4_diag0 of the self units, ONE radix sort of the followers of all units, segment resolution, entropy.  Two host
 // synchronisations per batch.  Leaves nhsp HSPs in hsps / hsp_unit (device).
+// How large the queues are, what an overflow teaches, when a batch is refused with MIMEO_ERR_SPLIT and how the arenas are
+// cut and grow is policy, written once in queue_plan.h: shares, boosts and learn(), initial_caps() / walk_cap() / grow(),
+// queue_slices() / arena_bytes() / queue_bytes(), sort_slices(), queue_budget() / must_split(), arena_want() and
+// follower_key_bits().  ExtBatch feeds it counters and free memory and makes the HIP calls.
+struct ExtQueues;     // k4_device.h
+struct ExtCounters;
+// development / test switches of a batch, read from the environment once per batch (k4_extend.hip: read_switches): MIMEO_HEAVY=v1,
+// MIMEO_K4_STATS, MIMEO_TRACE, MIMEO_K4_VARIANT, MIMEO_K34_DEBUG, MIMEO_QUEUE_SHRINK (smaller queues; tests: force the rerun),
+// MIMEO_QUEUE_BUDGET_MB (tests: force the split)
+struct ExtSwitches {
+    bool v1 = false, k4_stats = false, trace = false, budget_forced = false;
+    int k4_variant = 0;
+    uint32_t k34_dbg = 0;
+    double shrink = 1.0;
+    long budget_mb = 0;
+};
 struct ExtBatch {
-    DeviceBuf units, ctr, cand, fkey, fkey2, fprev, fprev2, medq, medu, longq, longu, walkq, flags, segs, tmp, nsel, bigseg, hsps,
-        hsp_unit, unit_hits, tile_hits, selfs, hits, bigcand, bigacc, heavy;
+    // mirror: mirror_dst_ on the device + one counter; plan_buf: the split pass's plan (k34_plan); funits: per-unit table of the heavy
+    // kernels (FusedUnit); nwalk_u: walk-queue counters per unit and shard + split-pass tile counts
+    DeviceBuf units, ctr, nsel, unit_hits, tile_hits, selfs, hits, bigcand, bigacc, heavy, mirror, plan_buf, funits, nwalk_u;
+    // hipMalloc / hipFree of tens of GB cost seconds (C5 at full size spent 80 % of its wall time there): the queues of a batch are
+    // slices of ONE allocation that only ever grows (arena_q, carved per batch: qbuf), the follower sort's buffers of another
+    // (arena_s: sbuf).  The 8 GiB and 4 GiB of head-room they leave when they grow differ on purpose: the queue arena is allocated
+    // first and leaves room for the sort arena too (queue_plan::arena_want).
+    DeviceBuf arena_q, arena_s;
+    DeviceBuf qbuf[queue_plan::Q_SLICES], sbuf[queue_plan::S_SLICES];
+    DeviceBuf &hsps = qbuf[queue_plan::Q_HSPS], &hsp_unit = qbuf[queue_plan::Q_HSP_UNIT];   // what the batch leaves to the pipeline
     JoinCtx jc;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<hipEvent_t> kev;     // an event pair per unit around its K34 launch
+    hipEvent_t ev[6] = {};           // 0, 1: around the heavy phase; 3, 2: around the tails; 4, 5: around the seed-scan kernel (both passes)
     hipStream_t side = nullptr;      // k4_diag0 of the self units runs beside the heavy kernels
     hipEvent_t side_done = nullptr;
     std::vector<unsigned long long> h_unit_hits;
-    // queue sizing: largest excess over the random-sequence shares seen so far, per queue (followers, walks beyond the frame,
-    // long walks, candidates, walk queue): microsatellites flood the follower queue alone (C5: half of all hits)
-    double boost_f = 1.0, boost_m = 1.0, boost_l = 1.0, boost_c = 1.0, boost_w = 1.0;
-    // ... within one API call: every call starts from the random-sequence shares.  Boosts learned on one input would size
-    // the queues of every later call on any other (a tandem-array job of 1e6 expected hits left boosts of ~100-300; the C4
-    // row after it was cut into 125 batches instead of one, and a C2 call after that asked for 190 GiB of queues)
-    void new_call() { boost_f = boost_m = boost_l = boost_c = boost_w = 1.0; }
+    // Boosts hold within one API call: every call starts from the random-sequence shares.  Boosts learned on one input would
+    // size the queues of every later call on any other (a tandem-array job of 1e6 expected hits left boosts of ~100-300; the C4
+    // row after it was cut into 125 batches instead of one, and a C2 call after that asked for 190 GiB of queues);
+    // microsatellites flood the follower queue alone (C5: half of all hits), hence one boost per queue
+    queue_plan::Boosts boost;
+    void new_call() { boost = queue_plan::Boosts(); }
     // run = start (sizes the queues, enqueues the heavy phase on the calling thread's stream, waits for nothing) + finish (the
     // tails on the same stream: two host round trips; a batch whose queues overflowed is repeated there with room).  The
     // pipeline only calls run, one batch at a time: a batch is finished before the next one starts.
@@ -229,33 +252,30 @@ struct ExtBatch {
     std::vector<uint32_t> h_selfs_, mirror_dst_;
     std::vector<UnitDesc> h_units_;
     std::vector<FusedUnit> h_funits_;
-    DeviceBuf mirror;     // mirror_dst_ on the device + one counter
-    // hipMalloc / hipFree of tens of GB cost seconds (C5 at full size spent 80 % of its wall time there): the queues of a batch are
-    // slices of ONE allocation that only ever grows (arena_q, carved per batch), the follower sort's buffers of another (arena_s)
-    DeviceBuf arena_q, arena_s;
-    DeviceBuf plan_buf;          // the split pass's plan (k34_plan)
-    DeviceBuf funits, nwalk_u;   // per-unit table of the heavy kernels (FusedUnit); walk-queue counters per unit and shard + split-pass tile counts
+    ExtSwitches sw_;
+    queue_plan::Caps cap_;
     std::vector<uint64_t> walk_cap_u_;   // walk-queue capacity per unit and shard
     uint64_t walk_entries_ = 0;          // ... all regions together
     uint32_t nactive_ = 0;               // units of the batch that launch the heavy kernels
     const unsigned int *plan_ctr_ = nullptr;   // the split pass plan's counters on the device (statistics)
-    uint64_t cap_f_ = 0, cap_m_ = 0, cap_l_ = 0, cap_c_ = 0;
-    double expect_hits_ = 0, shrink_ = 1.0;
-    uint32_t ebits_ = 0, dbits_ = 0, key_bits_ = 0;
-    bool v1_ = false, started_ = false, k4_stats_ = false, splittable_ = false;
-    uint32_t k34_dbg_ = 0;
-    int k4_variant_ = 0;
-    void *q_ = nullptr;   // ExtQueues of the batch (k4_device.h), owned
-    int enqueue_heavy();
-    void release_queues();          // the big queue buffers back to the device pool
-    uint64_t arena_bytes() const;   // device bytes of the batch's queues at the current capacities
-    uint64_t queue_bytes() const;   // device bytes the queues of the batch take at the current capacities
-    uint64_t held_bytes() const;    // ... and what its buffers hold already
+    double expect_hits_ = 0;
+    queue_plan::KeyBits key_ = {0, 0, 0, false};
+    bool started_ = false, splittable_ = false;
+    ExtQueues *q_ = nullptr;   // the queues as the kernels see them, owned
+    uint64_t arena_bytes() const { return queue_plan::arena_bytes(cap_, walk_entries_, !mirror_dst_.empty(), sw_.v1); }   // the queue arena at the current capacities
+    uint64_t queue_bytes() const { return queue_plan::queue_bytes(cap_, walk_entries_, !mirror_dst_.empty(), sw_.v1); }   // ... plus what the rest of the batch may ask for meanwhile
+    // the steps of start: the heavy phase of the batch on the calling thread's stream, with the current capacities = the queue
+    // arena's slices, then K34 and the walk-queue kernel over all units or, MIMEO_HEAVY=v1, join + fast kernel per unit
+    int enqueue_heavy(), carve_queues(), enqueue_k34(), enqueue_v1();
+    // ... and of finish
+    int tails(ExtCounters *c), resolve_followers(uint64_t nf), entropy(ExtCounters *c);
+    int print_stats(const ExtCounters &c, uint64_t nf, uint64_t nm, bool over);
+    int learn_and_grow(const queue_plan::Counts &fullest, const queue_plan::Counts &batch);
 };
 constexpr uint32_t NO_MIRROR = 0xFFFFFFFFu;
 constexpr int MIMEO_ERR_SPLIT = -100;   // internal: never crosses the C-ABI
 // largest batch the follower key can name for scaffolds of these lengths (unit bits = 64 - end bits - diagonal bits)
-uint32_t ext_batch_max_units(uint64_t max_tlen, uint64_t max_qlen);
+inline uint32_t ext_batch_max_units(uint64_t max_tlen, uint64_t max_qlen) { return queue_plan::max_units(max_tlen, max_qlen, SEED_LEN); }
 
 // K5/K6: one group = one (target scaffold, query scaffold, strand) with its HSP range
 constexpr int MAX_BATCH = 32;

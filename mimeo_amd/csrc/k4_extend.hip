@@ -806,79 +806,70 @@ int launch_fused_batch(const FusedUnit *d_units, uint32_t nactive, const ExtQueu
                        uint32_t dbg);
 void launch_sum_hits(const ExtQueues &q, uint32_t nunits, hipStream_t st);
 
+static_assert(sizeof(Cand) == queue_plan::CAND_BYTES && sizeof(mimeo_hsp) == queue_plan::HSP_BYTES, "queue_plan.h prices the candidate and HSP slices with these sizes");
+
 void ExtBatch::release() {
-    for (DeviceBuf *b : {&units, &ctr, &cand, &fkey, &fkey2, &fprev, &fprev2, &medq, &medu, &longq, &longu, &walkq, &flags, &segs, &tmp,
-                         &nsel, &bigseg, &hsps, &hsp_unit, &unit_hits, &tile_hits, &selfs, &hits, &bigcand, &bigacc, &heavy, &mirror, &funits, &nwalk_u, &plan_buf, &arena_q, &arena_s})
-        b->release();
+    for (DeviceBuf *b : {&units, &ctr, &nsel, &unit_hits, &tile_hits, &selfs, &hits, &bigcand, &bigacc, &heavy, &mirror, &funits, &nwalk_u, &plan_buf}) b->release();
+    for (DeviceBuf &b : qbuf) b.release();   // slices: nothing is freed here
+    for (DeviceBuf &b : sbuf) b.release();
+    arena_q.release(); arena_s.release();
     jc.release();
     for (auto &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    for (auto &e : kev) (void)hipEventDestroy(e);
-    kev.clear();
     if (side_done) { (void)hipEventDestroy(side_done); side_done = nullptr; }
     if (side) { (void)hipStreamDestroy(side); side = nullptr; }
-    delete (ExtQueues *)q_;
-    q_ = nullptr;
+    delete q_; q_ = nullptr;
     started_ = false;
 }
 
-static uint32_t bits_for(uint64_t v) {  // bits needed to hold values 0 .. v
-    uint32_t b = 1;
-    while (b < 64 && (v >> b)) b++;
-    return b;
-}
-
-uint32_t ext_batch_max_units(uint64_t max_tlen, uint64_t max_qlen) {
-    const uint32_t ebits = bits_for(max_tlen + SEED_LEN), dbits = bits_for(max_tlen + max_qlen + SEED_LEN);
-    const uint32_t ubits = 64 - std::min(63u, ebits + dbits);
-    return ubits >= 20 ? (1u << 20) : (1u << ubits);
-}
-
-int ExtBatch::run(const std::vector<UnitWork> &work, const mimeo_params *p, uint64_t *nhsp_out, ExtStats *stats,
-                  const std::vector<uint32_t> *mirror_dst) {
+int ExtBatch::run(const std::vector<UnitWork> &work, const mimeo_params *p, uint64_t *nhsp_out, ExtStats *stats, const std::vector<uint32_t> *mirror_dst) {
     *nhsp_out = 0;
-    if (work.empty()) return 0;
-    int rc = start(work, p, mirror_dst);
-    if (rc) return rc;
-    return finish(nhsp_out, stats);
+    const int rc = start(work, p, mirror_dst);
+    return rc ? rc : finish(nhsp_out, stats);
 }
 
-// Device bytes of the batch's queues at the current capacities: followers and walks beyond the frame in eight shards (key +
-// predecessor: 12 bytes / hit + walk state + unit: 20 bytes), long walks, candidates + HSPs (+ their mirror copies), the walk queue of one unit.  The
-// follower sort's second buffer, flags, segment lists and rocPRIM's scratch are sized by the followers actually seen
-// (finish()): up to 41 bytes each on top.
-uint64_t ExtBatch::arena_bytes() const {   // the queues proper: what the first arena holds
-    const uint64_t mf = mirror_dst_.empty() ? 1 : 2;
-    return cap_f_ * 8 * 12 + cap_m_ * 8 * 20 + cap_l_ * 12 + cap_c_ * (sizeof(Cand) + mf * (sizeof(mimeo_hsp) + 4)) + (v1_ ? 8 : walk_entries_ * 8) + 4096;
+static ExtSwitches read_switches() {
+    ExtSwitches s;
+    const char *e;
+    s.v1 = (e = getenv("MIMEO_HEAVY")) && !strcmp(e, "v1");
+    if ((e = getenv("MIMEO_K4_VARIANT"))) s.k4_variant = atoi(e);
+    if ((e = getenv("MIMEO_K34_DEBUG"))) s.k34_dbg = (uint32_t)atoi(e);
+    s.k4_stats = getenv("MIMEO_K4_STATS") != nullptr;
+    if ((e = getenv("MIMEO_QUEUE_SHRINK")) && atof(e) > 0) s.shrink = atof(e);
+    if ((e = getenv("MIMEO_QUEUE_BUDGET_MB"))) { s.budget_forced = true; s.budget_mb = atol(e); }
+    s.trace = getenv("MIMEO_TRACE") != nullptr;
+    return s;
 }
-// ... plus what the rest of the batch may ask for while they are alive: the follower sort's second arena at its worst (every
-// shard full: 41 bytes per follower) and the chain / gapped stage's scratch and alignment slots (~200 bytes per HSP, 60 more
-// where the chain stage meets large groups: k5_chain_wave's orders and tree)
-uint64_t ExtBatch::queue_bytes() const {
-    const uint64_t mf = mirror_dst_.empty() ? 1 : 2;
-    return arena_bytes() + cap_f_ * 8 * 41 + cap_c_ * mf * 260;
-}
-// carve `bytes` (rounded up to 256) off an arena at *off
-static void *carve(const DeviceBuf &arena, size_t *off, size_t bytes) {
-    void *p = (char *)arena.p + *off;
-    *off += (bytes + 255) & ~(size_t)255;
-    return p;
-}
-// the arenas back to the device pool (mimeo_shutdown, or a call that ends in an allocation failure)
-void ExtBatch::release_queues() {
-    for (DeviceBuf *d : {&cand, &fkey, &fkey2, &fprev, &fprev2, &medq, &medu, &longq, &longu, &walkq, &flags, &segs, &tmp, &bigseg, &hsps, &hsp_unit})
-        d->release();   // slices: nothing is freed here
-    arena_q.release();
-    arena_s.release();
-}
-uint64_t ExtBatch::held_bytes() const { return arena_q.cap + arena_s.cap; }
-// free device memory plus what the batch's own buffers would give back, less a reserve for chain / gapped scratch
+
+// what the queues of the batch may take of the device's memory now
 static int queue_budget(const ExtBatch &b, uint64_t *budget) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t have = (uint64_t)free_b + b.held_bytes(), reserve = std::min<uint64_t>(have / 8, 8ull << 30);
-    *budget = have - reserve;
-    if (getenv("MIMEO_QUEUE_BUDGET_MB")) *budget = (uint64_t)atol(getenv("MIMEO_QUEUE_BUDGET_MB")) << 20;   // tests: force the split
+    *budget = queue_plan::queue_budget(free_b, b.arena_q.cap + b.arena_s.cap, b.sw_.budget_forced, b.sw_.budget_mb);
     return 0;
+}
+
+// The slices of an arena at these sizes, one behind the other.  An arena that is too small drops its slices and grows
+// (queue_plan::arena_want; first_slack_div: the part of its size it takes on top the first time, 0: nothing); when the memory
+// is not there a batch that can be cut is cut.
+template <int N>
+static int lay_out(DeviceBuf &arena, DeviceBuf (&slices)[N], const uint64_t (&bytes)[N], uint64_t headroom, uint64_t first_slack_div, bool splittable) {
+    uint64_t off[N];
+    const size_t total = queue_plan::place_slices(bytes, off);
+    if (total > arena.cap) {
+        for (DeviceBuf &s : slices) s.release();
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const size_t want = queue_plan::arena_want(total, arena.cap, free_b, headroom, first_slack_div ? total / first_slack_div : 0);
+        int rc = arena.reserve(want);
+        if (rc && want > total) rc = arena.reserve(total);
+        if (rc) return rc == MIMEO_ERR_NOMEM && splittable ? MIMEO_ERR_SPLIT : rc;
+    }
+    for (int i = 0; i < N; i++) slices[i].set_view((char *)arena.p + off[i], bytes[i]);
+    return 0;
+}
+
+static queue_plan::Counts counts_of(const ExtCounters &c, uint64_t followers, uint64_t generic) {
+    return queue_plan::Counts{followers, generic, c.nlong, c.ncand, c.nwalk_total, c.nwalk_over};
 }
 
 int ExtBatch::start(const std::vector<UnitWork> &work, const mimeo_params *p, const std::vector<uint32_t> *mirror_dst) {
@@ -886,91 +877,58 @@ int ExtBatch::start(const std::vector<UnitWork> &work, const mimeo_params *p, co
     started_ = false;
     const uint32_t nunits = (uint32_t)work.size();
     if (!nunits) return 0;
-    w_ = work;
-    p_ = *p;
+    w_ = work; p_ = *p;
+    sw_ = read_switches();
     uint64_t max_t = 0, max_q = 0;
-    double expect_hits = 0;
-    std::vector<UnitDesc> &h_units = h_units_;   // a member: the copy below is asynchronous
-    h_units.resize(nunits);
+    uint32_t launching = 0;
+    expect_hits_ = 0;
+    h_units_.resize(nunits);   // a member: the copy below is asynchronous
     h_selfs_.clear();
+    walk_cap_u_.assign(nunits, 0);
     for (uint32_t u = 0; u < nunits; u++) {
         const UnitWork &w = work[u];
         if (w.d.T.len >= 0x7FFFFF00u || w.d.Q.len >= 0x7FFFFF00u) { set_error("scaffold longer than 2^31 bases"); return MIMEO_ERR_LIMIT; }
-        h_units[u] = w.d;
-        max_t = std::max<uint64_t>(max_t, w.d.T.len);
-        max_q = std::max<uint64_t>(max_q, w.d.Q.len);
-        expect_hits += host_plan::expected_seed_hits(w.ti.n, w.qi.n);
+        h_units_[u] = w.d;
+        max_t = std::max<uint64_t>(max_t, w.d.T.len); max_q = std::max<uint64_t>(max_q, w.d.Q.len);
         if (w.d.same) h_selfs_.push_back(u);
+        if (!w.ti.n || !w.qi.n) continue;   // a mirror rider: expects no hits, launches nothing
+        const double e = host_plan::expected_seed_hits(w.ti.n, w.qi.n);
+        expect_hits_ += e;
+        walk_cap_u_[u] = queue_plan::walk_cap(e, boost, sw_.shrink);
+        launching++;
     }
-    expect_hits_ = expect_hits;
-    {   // a batch can be cut in two when at least two of its units launch the heavy kernels (a mirror unit rides with its source)
-        uint32_t launching = 0;
-        for (uint32_t u = 0; u < nunits; u++) launching += (work[u].ti.n && work[u].qi.n) ? 1u : 0u;
-        splittable_ = launching > 1;
-    }
+    splittable_ = launching > 1;   // a batch can be cut in two when at least two of its units launch the heavy kernels (a rider stays with its source)
     mirror_dst_.clear();
     if (mirror_dst && std::any_of(mirror_dst->begin(), mirror_dst->end(), [](uint32_t m) { return m != NO_MIRROR; })) {
         if (mirror_dst->size() != nunits) { set_error("internal: mirror table of the wrong size"); return MIMEO_ERR_ARG; }
         mirror_dst_ = *mirror_dst;
     }
-    ebits_ = bits_for(max_t + SEED_LEN);
-    dbits_ = bits_for(max_t + max_q + SEED_LEN);
-    if (ebits_ + dbits_ > 63 || (nunits > 1 && bits_for(nunits - 1) + ebits_ + dbits_ > 64)) {
-        set_error("internal: batch too large for the follower key");
-        return MIMEO_ERR_ARG;
-    }
-    key_bits_ = std::min(64u, ebits_ + dbits_ + (nunits > 1 ? bits_for(nunits - 1) : 0));
+    key_ = queue_plan::follower_key_bits(max_t, max_q, nunits, SEED_LEN);
+    if (!key_.fits) { set_error("internal: batch too large for the follower key"); return MIMEO_ERR_ARG; }
     if (!ev[0]) {
         for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
         HIP_TRY(hipEventCreateWithFlags(&side_done, hipEventDisableTiming));
         HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
     }
-    // development / test switches: read once per batch, never per launch
-    v1_ = getenv("MIMEO_HEAVY") && !strcmp(getenv("MIMEO_HEAVY"), "v1");
-    k34_dbg_ = getenv("MIMEO_K34_DEBUG") ? (uint32_t)atoi(getenv("MIMEO_K34_DEBUG")) : 0u;
-    k4_variant_ = getenv("MIMEO_K4_VARIANT") ? atoi(getenv("MIMEO_K4_VARIANT")) : 0;
-    k4_stats_ = getenv("MIMEO_K4_STATS") != nullptr;
     int rc;
-    if ((rc = units.reserve((size_t)nunits * sizeof(UnitDesc))) || (rc = ctr.reserve(sizeof(ExtCounters))) ||
-        (rc = unit_hits.reserve((size_t)nunits * 8)) || (rc = nsel.reserve(16)) ||
-        (rc = tile_hits.reserve(v1_ ? 8 : (size_t)nunits * NTILE * 8)) || (rc = bigcand.reserve((size_t)ENT_BIGCAP * 8)) ||
-        (rc = bigacc.reserve((size_t)ENT_BIGCAP * 5 * 8)) ||
-        (rc = selfs.reserve((h_selfs_.size() + 1) * 4)))
+    if ((rc = units.reserve((size_t)nunits * sizeof(UnitDesc))) || (rc = ctr.reserve(sizeof(ExtCounters))) || (rc = unit_hits.reserve((size_t)nunits * 8)) ||
+        (rc = nsel.reserve(16)) || (rc = tile_hits.reserve(sw_.v1 ? 8 : (size_t)nunits * NTILE * 8)) || (rc = bigcand.reserve((size_t)ENT_BIGCAP * 8)) ||
+        (rc = bigacc.reserve((size_t)ENT_BIGCAP * 5 * 8)) || (rc = selfs.reserve((h_selfs_.size() + 1) * 4)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(units.p, h_units.data(), (size_t)nunits * sizeof(UnitDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(units.p, h_units_.data(), (size_t)nunits * sizeof(UnitDesc), hipMemcpyHostToDevice, st));
     if (!h_selfs_.empty()) HIP_TRY(hipMemcpyAsync(selfs.p, h_selfs_.data(), h_selfs_.size() * 4, hipMemcpyHostToDevice, st));
-    // Queue capacities from the hit count expected on random sequence; a batch that does not fit (repeat-rich
-    // units) is repeated with room for everything the counters saw.  On random sequence 0.65 % of the hits
-    // are followers, ~1 % outlive the frame and 1e-4 become candidates.
-    const double shrink = getenv("MIMEO_QUEUE_SHRINK") ? atof(getenv("MIMEO_QUEUE_SHRINK")) : 1.0;  // tests: force the rerun
-    shrink_ = shrink > 0 ? shrink : 1.0;
-    // `boost`: the largest excess over these shares that an earlier batch showed (a repeat-rich genome overflows the
-    // first batch once, not every batch)
-    // (followers and generic-walk hits: capacity PER SHARD, eight shards, with half as much again for their imbalance)
-    cap_f_ = (uint64_t)(expect_hits * 0.02 / 8 * 1.5 * boost_f / shrink) + (uint64_t)(1048576 / shrink) + 64;
-    cap_m_ = (uint64_t)(expect_hits * 0.03 / 8 * 1.5 * boost_m / shrink) + (uint64_t)(1048576 / shrink) + 64;
-    cap_l_ = (uint64_t)(expect_hits * 0.002 * boost_l / shrink) + (uint64_t)(1048576 / shrink) + 64;
-    cap_c_ = (uint64_t)(expect_hits * 0.002 * boost_c / shrink) + (uint64_t)(1048576 / shrink) + 64;
-    // the walk queue: a region of eight shards per unit, sized from the unit's expected hits (K34 passes ~4 % of the hits of
-    // random sequence on)
-    walk_entries_ = 0;
-    walk_cap_u_.assign(nunits, 0);
-    for (uint32_t u = 0; u < nunits; u++) {
-        const UnitWork &w = work[u];
-        if (!w.ti.n || !w.qi.n) continue;
-        const double e = host_plan::expected_seed_hits(w.ti.n, w.qi.n);
-        walk_cap_u_[u] = (uint64_t)(e * 0.08 / 8 * 1.5 * boost_w / shrink) + (uint64_t)(16384 / shrink) + 64;
-        walk_entries_ += 8 * walk_cap_u_[u];
-    }
-    {   // a batch whose queues cannot fit is cut in two by the caller before anything is allocated (a single unit is tried anyway)
-        uint64_t budget = 0;
-        if ((rc = queue_budget(*this, &budget))) return rc;
-        if (getenv("MIMEO_TRACE"))
-            fprintf(stderr, "[trace] batch of %u units, %.3g expected hits: queues %.2f GiB of %.2f GiB budget (boosts f %.1f m %.1f l %.1f c %.1f w %.1f; caps f %llu m %llu l %llu c %llu walk entries %llu)\n", nunits, expect_hits,
-                    (double)queue_bytes() / (1 << 30), (double)budget / (1 << 30), boost_f, boost_m, boost_l, boost_c, boost_w,
-                    (unsigned long long)cap_f_, (unsigned long long)cap_m_, (unsigned long long)cap_l_, (unsigned long long)cap_c_, (unsigned long long)walk_entries_);
-        if (splittable_ && queue_bytes() > budget) return MIMEO_ERR_SPLIT;
-    }
+    // queue capacities from the hit count expected on random sequence; a batch that does not fit them (repeat-rich units) is
+    // repeated in finish() with room for everything the counters saw
+    cap_ = queue_plan::initial_caps(expect_hits_, boost, sw_.shrink);
+    walk_entries_ = queue_plan::walk_entries(walk_cap_u_);
+    // a batch whose queues cannot fit is cut in two by the caller before anything is allocated
+    uint64_t budget = 0;
+    if ((rc = queue_budget(*this, &budget))) return rc;
+    if (sw_.trace)
+        fprintf(stderr, "[trace] batch of %u units, %.3g expected hits: queues %.2f GiB of %.2f GiB budget (boosts f %.1f m %.1f l %.1f c %.1f w %.1f; caps f %llu m %llu l %llu c %llu walk entries %llu)\n", nunits, expect_hits_,
+                (double)queue_bytes() / (1 << 30), (double)budget / (1 << 30), boost.f, boost.m, boost.l, boost.c, boost.w,
+                (unsigned long long)cap_.f, (unsigned long long)cap_.m, (unsigned long long)cap_.l, (unsigned long long)cap_.c, (unsigned long long)walk_entries_);
+    if (queue_plan::must_split(splittable_, queue_bytes(), budget)) return MIMEO_ERR_SPLIT;
     if (!mirror_dst_.empty()) {
         if ((rc = mirror.reserve((size_t)nunits * 4 + 16))) return rc;
         HIP_TRY(hipMemcpyAsync(mirror.p, mirror_dst_.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, st));
@@ -981,155 +939,217 @@ int ExtBatch::start(const std::vector<UnitWork> &work, const mimeo_params *p, co
     return 0;
 }
 
-// the heavy phase of the batch on the calling thread's stream, with the current capacities
+// the queues of the batch: slices of the queue arena at the current capacities, and the kernels' view of them
+int ExtBatch::carve_queues() {
+    using namespace queue_plan;
+    ExtQueues &q = *q_;
+    memset(&q, 0, sizeof q);
+    q.ebits = key_.ebits; q.dbits = key_.dbits;
+    const int rc = lay_out(arena_q, qbuf, queue_slices(cap_, walk_entries_, !mirror_dst_.empty(), sw_.v1).bytes, queue_bytes() - arena_bytes() + QUEUE_ARENA_HEADROOM, 0, splittable_);
+    if (rc) return rc;
+    q.ctr = (ExtCounters *)ctr.p;
+    q.cand = (Cand *)qbuf[Q_CAND].p; q.fkey = (uint64_t *)qbuf[Q_FKEY].p; q.fprev = (uint32_t *)qbuf[Q_FPREV].p;
+    q.medq = (uint4 *)qbuf[Q_MEDQ].p; q.medu = (uint32_t *)qbuf[Q_MEDU].p; q.longq = (uint2 *)qbuf[Q_LONGQ].p; q.longu = (uint32_t *)qbuf[Q_LONGU].p;
+    q.bigcand = (unsigned long long *)bigcand.p; q.bigacc = (unsigned long long *)bigacc.p;
+    q.unit_hits = (unsigned long long *)unit_hits.p; q.tile_hits = (unsigned long long *)tile_hits.p;
+    q.walkq = (uint2 *)qbuf[Q_WALKQ].p;
+    q.cand_cap = cap_.c; q.follow_cap = cap_.f; q.med_cap = cap_.m; q.long_cap = cap_.l; q.walk_cap = 0;
+    return 0;
+}
+
 int ExtBatch::enqueue_heavy() {
     hipStream_t st = stream();
     const uint32_t nunits = (uint32_t)w_.size();
-    const mimeo_params *p = &p_;
-    const uint32_t *tab = group_table_device();
-    if (!tab) { set_error("group table upload failed"); return MIMEO_ERR_HIP; }
-    ExtQueues &q = *(ExtQueues *)q_;
-    memset(&q, 0, sizeof q);
-    q.ebits = ebits_; q.dbits = dbits_;
-    const uint64_t cap_f = cap_f_, cap_m = cap_m_, cap_l = cap_l_, cap_c = cap_c_;
-    const bool v1 = v1_;
-    const std::vector<UnitWork> &work = w_;
-    const std::vector<uint32_t> &h_selfs = h_selfs_;
+    if (!group_table_device()) { set_error("group table upload failed"); return MIMEO_ERR_HIP; }
     int rc;
-    {
-        {   // the queues of the batch: slices of one allocation (it grows when a batch needs more, with room to spare, and stays)
-            const size_t mf = mirror_dst_.empty() ? 1 : 2;
-            const size_t sz[10] = {cap_f * 8 * 8, cap_f * 8 * 4, cap_m * 8 * 16, cap_m * 8 * 4, cap_l * 8, cap_l * 4, cap_c * sizeof(Cand),
-                                   cap_c * sizeof(mimeo_hsp) * mf, cap_c * 4 * mf, v1 ? 8 : walk_entries_ * 8 + 8};
-            size_t total = 0;
-            for (size_t z : sz) total += (z + 255) & ~(size_t)255;
-            if (total > arena_q.cap) {
-                for (DeviceBuf *d : {&fkey, &fprev, &medq, &medu, &longq, &longu, &cand, &hsps, &hsp_unit, &walkq}) d->release();
-                // grow with room to spare when the device has it (the next overflow should not allocate again)
-                size_t free_b = 0, total_b = 0;
-                HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-                const size_t have = free_b + arena_q.cap;
-                // the first allocation is what the batch asks for; one that has to grow (an overflow, a larger batch) takes half as much
-                // again when the device has it, so that the next one does not allocate (hipMalloc costs ~35 ms per GiB)
-                size_t want = arena_q.cap ? total + total / 2 : total;
-                if (want + (queue_bytes() - arena_bytes()) + (8ull << 30) > have) want = total;   // the sort arena and the chain scratch come after
-                if ((rc = arena_q.reserve(want)) && want > total) rc = arena_q.reserve(total);
-                if (rc) return rc == MIMEO_ERR_NOMEM && splittable_ ? MIMEO_ERR_SPLIT : rc;
-            }
-            size_t off = 0;
-            DeviceBuf *bufs[10] = {&fkey, &fprev, &medq, &medu, &longq, &longu, &cand, &hsps, &hsp_unit, &walkq};
-            for (int i = 0; i < 10; i++) bufs[i]->set_view(carve(arena_q, &off, sz[i]), sz[i]);
-        }
-        q.ctr = (ExtCounters *)ctr.p;
-        q.cand = (Cand *)cand.p; q.fkey = (uint64_t *)fkey.p; q.fprev = (uint32_t *)fprev.p;
-        q.medq = (uint4 *)medq.p; q.medu = (uint32_t *)medu.p; q.longq = (uint2 *)longq.p; q.longu = (uint32_t *)longu.p;
-        q.bigcand = (unsigned long long *)bigcand.p; q.bigacc = (unsigned long long *)bigacc.p;
-        q.unit_hits = (unsigned long long *)unit_hits.p;
-        q.tile_hits = (unsigned long long *)tile_hits.p;
-        q.walkq = (uint2 *)walkq.p;
-        q.cand_cap = cap_c; q.follow_cap = cap_f; q.med_cap = cap_m; q.long_cap = cap_l; q.walk_cap = 0;
-        const UnitDesc *d_units = (const UnitDesc *)units.p;
-        HIP_TRY(hipMemsetAsync(ctr.p, 0, sizeof(ExtCounters), st));
-        HIP_TRY(hipMemsetAsync(unit_hits.p, 0, (size_t)nunits * 8, st));
-        if (!v1) HIP_TRY(hipMemsetAsync(tile_hits.p, 0, (size_t)nunits * NTILE * 8, st));   // K34 adds to it: a tile's pairs, wavefront by wavefront
-        HIP_TRY(hipMemsetAsync(nsel.p, 0, 16, st));
-        HIP_TRY(hipMemsetAsync(bigacc.p, 0, (size_t)ENT_BIGCAP * 5 * 8, st));
-        HIP_TRY(hipEventRecord(ev[0], st));
-        // the main diagonals of the self units: one wavefront each, beside the heavy kernels
-        if (!h_selfs.empty()) {
-            HIP_TRY(hipStreamWaitEvent(side, ev[0], 0));
-            hipLaunchKernelGGL(k4_diag0, dim3((uint32_t)h_selfs.size()), dim3(64), 0, side, d_units, (const uint32_t *)selfs.p, q,
-                               p->xdrop, p->hspthresh, p->transitions);
-            HIP_TRY(hipEventRecord(side_done, side));
-        }
-        // ---- heavy phase, nothing read back
-        if (!v1) {
-            // K34 over every unit of the batch in ONE launch (plus its split pass), then the hits it could not dismiss (3-4 % on
-            // random sequence, most of them false alarms of its cheap filter) through the sharp filter and the exact walk of
-            // round 1's fast kernel, again one launch for all units (grid.y = unit), then the walk-queue statistics
-            std::vector<FusedUnit> h_fu;
-            bool slim = true;
-            uint64_t base = 0;
-            for (uint32_t u = 0; u < nunits; u++) {
-                const UnitWork &w = work[u];
-                if (!w.ti.n || !w.qi.n) continue;
-                FusedUnit f;
-                memset(&f, 0, sizeof f);
-                f.T = w.ti; f.Q = w.qi; f.Tv = w.d.T; f.Qv = w.d.Q; f.unit = u; f.same = w.d.same;
-                f.walk_base = base; f.walk_cap = walk_cap_u_[u];
-                base += 8 * f.walk_cap;
-                slim = slim && !w.d.T.has_n && !w.d.Q.has_n;
-                h_fu.push_back(f);
-            }
-            const uint32_t nactive = (uint32_t)h_fu.size();
-            nactive_ = nactive;
-            if (nactive) {
-                h_funits_ = std::move(h_fu);   // a member: the copy below is asynchronous
-                // counters: 8 walk-queue shards per unit, then the split-pass tile counts
-                // the split pass's tile lists (number + estimate per slot) and its plan (dense tiles, part bases, splits, counters)
-                const size_t slots = (size_t)std::min(nactive, 32768u) * NTILE;
-                if ((rc = funits.reserve((size_t)nactive * sizeof(FusedUnit))) || (rc = nwalk_u.reserve((size_t)nactive * 9 * 8)) ||
-                    (rc = heavy.reserve((size_t)nactive * NTILE * 12)) || (rc = plan_buf.reserve(slots * 28 + 4096)))
-                    return rc == MIMEO_ERR_NOMEM && splittable_ ? MIMEO_ERR_SPLIT : rc;
-                q.heavy_est = (unsigned long long *)heavy.p;
-                q.heavy = (uint32_t *)(q.heavy_est + (size_t)nactive * NTILE);
-                HeavyPlan plan;
-                plan.est = q.heavy_est;
-                plan.split = (uint4 *)plan_buf.p;                       // slots * 16
-                plan.tile = (uint2 *)(plan.split + slots);              // slots * 8
-                plan.base = (uint32_t *)(plan.tile + slots);            // (slots + 1) * 4
-                plan.ctr = (unsigned int *)(plan.base + slots + 4);     // 3 counters
-                plan_ctr_ = plan.ctr;
-                q.nwalk_u = (unsigned long long *)nwalk_u.p;
-                q.nheavy_u = q.nwalk_u + (size_t)nactive * 8;
-                HIP_TRY(hipMemcpyAsync(funits.p, h_funits_.data(), (size_t)nactive * sizeof(FusedUnit), hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemsetAsync(nwalk_u.p, 0, (size_t)nactive * 9 * 8, st));
-                while (kev.size() < 2) {   // an event pair around the seed-scan kernel (both passes)
-                    hipEvent_t e;
-                    HIP_TRY(hipEventCreate(&e));
-                    kev.push_back(e);
-                }
-                HIP_TRY(hipEventRecord(kev[0], st));
-                if ((rc = launch_fused_batch((const FusedUnit *)funits.p, nactive, q, plan, p, st, k34_dbg_))) return rc;
-                HIP_TRY(hipEventRecord(kev[1], st));
-                for (uint32_t u0 = 0; u0 < nactive; u0 += 32768u) {
-                    const uint32_t nu = std::min(32768u, nactive - u0);
-                    ExtQueues qq = q;
-                    qq.nwalk_u = q.nwalk_u + (size_t)u0 * 8;
-                    const FusedUnit *fu = (const FusedUnit *)funits.p + u0;
-                    // a unit's queue is worked off by at most 256 workgroups (their end-of-kernel flushes are same-address
-                    // atomics: more workgroups cost more than they bring), fewer when many small units share the launch
-                    const uint32_t qblocks = std::max(1u, std::min(256u, (8192u + nu - 1) / nu));
-                    if (slim) hipLaunchKernelGGL(k4_walk_batch<9>, dim3(qblocks, nu), dim3(FAST_THREADS), 0, st, fu, p->xdrop, p->hspthresh, p->transitions, tab, qq);
-                    else hipLaunchKernelGGL(k4_walk_batch<5>, dim3(qblocks, nu), dim3(FAST_THREADS), 0, st, fu, p->xdrop, p->hspthresh, p->transitions, tab, qq);
-                }
-                hipLaunchKernelGGL(k4_walk_summary, dim3(std::min(256u, (nactive * 8u + 255u) / 256u)), dim3(256), 0, st, (const FusedUnit *)funits.p, nactive,
-                                   (const unsigned long long *)q.nwalk_u, q.ctr);
-            }
-        } else {
-            for (uint32_t u = 0; u < nunits; u++) {
-                const UnitWork &w = work[u];
-                if (!w.ti.n || !w.qi.n) continue;
-                // A/B path: materialise the hits (exact count: one round trip per unit), then the round-1 fast kernel
-                uint64_t nh = 0;
-                if ((rc = join_hits(jc, w.ti, w.qi, p->transitions, hits, &nh, nullptr))) return rc;
-                if (!nh) continue;
-                uint64_t nb = std::min<uint64_t>((nh + FAST_THREADS - 1) / FAST_THREADS, 1024);
-                const int variant = k4_variant_;
-                const bool slim = !w.d.T.has_n && !w.d.Q.has_n;
-#define K4_LAUNCH(V) hipLaunchKernelGGL(k4_extend_hits<V>, dim3((uint32_t)nb), dim3(FAST_THREADS), 0, st, w.d.T, w.d.Q, (const uint2 *)hits.p, nh, \
-                           p->xdrop, p->hspthresh, p->transitions, tab, q, u, (int)w.d.same)
-                if (variant == 1) K4_LAUNCH(1);
-                else if (variant == 5 || !slim) K4_LAUNCH(5);
-                else K4_LAUNCH(9);
-#undef K4_LAUNCH
-            }
-        }
-        if (!v1) launch_sum_hits(q, nunits, st);
-        HIP_TRY(hipEventRecord(ev[1], st));
+    if ((rc = carve_queues())) return rc;
+    HIP_TRY(hipMemsetAsync(ctr.p, 0, sizeof(ExtCounters), st));
+    HIP_TRY(hipMemsetAsync(unit_hits.p, 0, (size_t)nunits * 8, st));
+    if (!sw_.v1) HIP_TRY(hipMemsetAsync(tile_hits.p, 0, (size_t)nunits * NTILE * 8, st));   // K34 adds to it: a tile's pairs, wavefront by wavefront
+    HIP_TRY(hipMemsetAsync(nsel.p, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(bigacc.p, 0, (size_t)ENT_BIGCAP * 5 * 8, st));
+    HIP_TRY(hipEventRecord(ev[0], st));
+    if (!h_selfs_.empty()) {   // the main diagonals of the self units: one wavefront each, beside the heavy kernels
+        HIP_TRY(hipStreamWaitEvent(side, ev[0], 0));
+        hipLaunchKernelGGL(k4_diag0, dim3((uint32_t)h_selfs_.size()), dim3(64), 0, side, (const UnitDesc *)units.p, (const uint32_t *)selfs.p, *q_, p_.xdrop, p_.hspthresh, p_.transitions);
+        HIP_TRY(hipEventRecord(side_done, side));
     }
+    if ((rc = sw_.v1 ? enqueue_v1() : enqueue_k34())) return rc;   // the heavy phase: nothing is read back
+    HIP_TRY(hipEventRecord(ev[1], st));
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// K34 over every unit of the batch in ONE launch (plus its split pass), then the hits it could not dismiss (3-4 % on random
+// sequence, most of them false alarms of its cheap filter) through the sharp filter and the exact walk of round 1's fast
+// kernel, again one launch for all units (grid.y = unit), then the walk-queue statistics and the hit counts per unit
+int ExtBatch::enqueue_k34() {
+    hipStream_t st = stream();
+    const uint32_t *tab = group_table_device();
+    ExtQueues &q = *q_;
+    h_funits_.clear();   // a member: the copy below is asynchronous
+    bool slim = true;
+    uint64_t base = 0;
+    for (uint32_t u = 0; u < (uint32_t)w_.size(); u++) {
+        const UnitWork &w = w_[u];
+        if (!w.ti.n || !w.qi.n) continue;
+        FusedUnit f; memset(&f, 0, sizeof f);
+        f.T = w.ti; f.Q = w.qi; f.Tv = w.d.T; f.Qv = w.d.Q; f.unit = u; f.same = w.d.same;
+        f.walk_base = base; f.walk_cap = walk_cap_u_[u];
+        base += queue_plan::SHARDS * f.walk_cap;
+        slim = slim && !w.d.T.has_n && !w.d.Q.has_n;
+        h_funits_.push_back(f);
+    }
+    const uint32_t nactive = nactive_ = (uint32_t)h_funits_.size();
+    if (nactive) {
+        // the split pass's tile lists (number + estimate per slot) and its plan (dense tiles, part bases, splits, counters)
+        const size_t slots = (size_t)std::min(nactive, 32768u) * NTILE;
+        int rc;
+        if ((rc = funits.reserve((size_t)nactive * sizeof(FusedUnit))) || (rc = nwalk_u.reserve((size_t)nactive * 9 * 8)) ||
+            (rc = heavy.reserve((size_t)nactive * NTILE * 12)) || (rc = plan_buf.reserve(slots * 28 + 4096)))
+            return rc == MIMEO_ERR_NOMEM && splittable_ ? MIMEO_ERR_SPLIT : rc;
+        q.heavy_est = (unsigned long long *)heavy.p;
+        q.heavy = (uint32_t *)(q.heavy_est + (size_t)nactive * NTILE);
+        HeavyPlan plan;
+        plan.est = q.heavy_est;
+        plan.split = (uint4 *)plan_buf.p;                       // slots * 16
+        plan.tile = (uint2 *)(plan.split + slots);              // slots * 8
+        plan.base = (uint32_t *)(plan.tile + slots);            // (slots + 1) * 4
+        plan.ctr = (unsigned int *)(plan.base + slots + 4);     // 3 counters
+        plan_ctr_ = plan.ctr;
+        q.nwalk_u = (unsigned long long *)nwalk_u.p;            // 8 walk-queue shards per unit, then the split-pass tile counts
+        q.nheavy_u = q.nwalk_u + (size_t)nactive * 8;
+        HIP_TRY(hipMemcpyAsync(funits.p, h_funits_.data(), (size_t)nactive * sizeof(FusedUnit), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(nwalk_u.p, 0, (size_t)nactive * 9 * 8, st));
+        HIP_TRY(hipEventRecord(ev[4], st));
+        if ((rc = launch_fused_batch((const FusedUnit *)funits.p, nactive, q, plan, &p_, st, sw_.k34_dbg))) return rc;
+        HIP_TRY(hipEventRecord(ev[5], st));
+        for (uint32_t u0 = 0; u0 < nactive; u0 += 32768u) {
+            const uint32_t nu = std::min(32768u, nactive - u0);
+            ExtQueues qq = q;
+            qq.nwalk_u = q.nwalk_u + (size_t)u0 * 8;
+            const FusedUnit *fu = (const FusedUnit *)funits.p + u0;
+            // a unit's queue is worked off by at most 256 workgroups (their end-of-kernel flushes are same-address
+            // atomics: more workgroups cost more than they bring), fewer when many small units share the launch
+            const uint32_t qblocks = std::max(1u, std::min(256u, (8192u + nu - 1) / nu));
+            if (slim) hipLaunchKernelGGL(k4_walk_batch<9>, dim3(qblocks, nu), dim3(FAST_THREADS), 0, st, fu, p_.xdrop, p_.hspthresh, p_.transitions, tab, qq);
+            else hipLaunchKernelGGL(k4_walk_batch<5>, dim3(qblocks, nu), dim3(FAST_THREADS), 0, st, fu, p_.xdrop, p_.hspthresh, p_.transitions, tab, qq);
+        }
+        hipLaunchKernelGGL(k4_walk_summary, dim3(std::min(256u, (nactive * 8u + 255u) / 256u)), dim3(256), 0, st, (const FusedUnit *)funits.p, nactive,
+                           (const unsigned long long *)q.nwalk_u, q.ctr);
+    }
+    launch_sum_hits(q, (uint32_t)w_.size(), st);
+    return 0;
+}
+
+// MIMEO_HEAVY=v1, the A/B path: per unit, materialise the hits (exact count: one round trip), then the round-1 fast kernel
+int ExtBatch::enqueue_v1() {
+    for (uint32_t u = 0; u < (uint32_t)w_.size(); u++) {
+        const UnitWork &w = w_[u];
+        if (!w.ti.n || !w.qi.n) continue;
+        uint64_t nh = 0;
+        const int rc = join_hits(jc, w.ti, w.qi, p_.transitions, hits, &nh, nullptr);
+        if (rc) return rc;
+        if (!nh) continue;
+        const bool slim = !w.d.T.has_n && !w.d.Q.has_n;
+#define K4_LAUNCH(V) hipLaunchKernelGGL(k4_extend_hits<V>, dim3((uint32_t)std::min<uint64_t>((nh + FAST_THREADS - 1) / FAST_THREADS, 1024)), dim3(FAST_THREADS), 0, stream(), \
+                           w.d.T, w.d.Q, (const uint2 *)hits.p, nh, p_.xdrop, p_.hspthresh, p_.transitions, group_table_device(), *q_, u, (int)w.d.same)
+        if (sw_.k4_variant == 1) K4_LAUNCH(1);
+        else if (sw_.k4_variant == 5 || !slim) K4_LAUNCH(5);
+        else K4_LAUNCH(9);
+#undef K4_LAUNCH
+    }
+    return 0;
+}
+
+// ---- the tails, once per batch: the steps of finish()
+// walks beyond the frame; round trip 1: the follower count (sizes the sort) and the overflow check
+int ExtBatch::tails(ExtCounters *c) {
+    hipStream_t st = stream();
+    const UnitDesc *d_units = (const UnitDesc *)units.p;
+    HIP_TRY(hipStreamWaitEvent(st, ev[1], 0));   // the heavy phase may have run on another stream
+    HIP_TRY(hipEventRecord(ev[3], st));
+    hipLaunchKernelGGL(k4_extend_generic, dim3(generic_grid()), dim3(EXT_THREADS), 0, st, d_units, *q_, p_.xdrop, p_.hspthresh, p_.transitions, group_table_device());
+    if (!h_selfs_.empty()) HIP_TRY(hipStreamWaitEvent(st, side_done, 0));
+    hipLaunchKernelGGL(k4_extend_long, dim3(768), dim3(EXT_THREADS), 0, st, d_units, *q_, p_.xdrop, p_.hspthresh, p_.transitions);
+    HIP_TRY(hipMemcpyAsync(c, ctr.p, sizeof *c, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// the nf followers of all units: gathered, sorted by (unit, diagonal, seed end), cut into segments and resolved
+int ExtBatch::resolve_followers(uint64_t nf) {
+    using namespace queue_plan;
+    hipStream_t st = stream();
+    const UnitDesc *d_units = (const UnitDesc *)units.p;
+    const ExtQueues &q = *q_;
+    // the sort's second buffers, flags, segment lists and rocPRIM's scratch: slices of the sort arena
+    size_t t1 = 0, t2 = 0;
+    rocprim::counting_iterator<uint64_t> iota(0);
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)nf, 0, key_.key_bits, st));
+    HIP_TRY(rocprim::select(nullptr, t2, iota, (uint8_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nsel.p, (size_t)nf, st));
+    const int rc = lay_out(arena_s, sbuf, sort_slices(nf, std::max(t1, t2)).bytes, SORT_ARENA_HEADROOM, 8, splittable_);
+    if (rc) return rc;
+    uint64_t *fkey = (uint64_t *)qbuf[Q_FKEY].p, *fkey2 = (uint64_t *)sbuf[S_FKEY2].p, *segs = (uint64_t *)sbuf[S_SEGS].p, *bigseg = (uint64_t *)sbuf[S_BIGSEG].p;
+    uint32_t *fprev = (uint32_t *)qbuf[Q_FPREV].p, *fprev2 = (uint32_t *)sbuf[S_FPREV2].p;
+    uint8_t *flags = (uint8_t *)sbuf[S_FLAGS].p;
+    const uint64_t *nseg = (const uint64_t *)nsel.p;
+    // the eight shards gathered into fkey2 / fprev2; the sort writes back into the (now free) shard area
+    hipLaunchKernelGGL(k4_compact_followers, dim3(1024), dim3(256), 0, st, q, fkey2, fprev2);
+    HIP_TRY(rocprim::radix_sort_pairs(sbuf[S_TMP].p, t1, fkey2, fkey, fprev2, fprev, (size_t)nf, 0, key_.key_bits, st));
+    hipLaunchKernelGGL(k4_segment_flags, dim3((uint32_t)((nf + 255) / 256)), dim3(256), 0, st, (const uint64_t *)fkey, (const uint32_t *)fprev, nf, q, flags);
+    HIP_TRY(rocprim::select(sbuf[S_TMP].p, t2, iota, flags, segs, (uint64_t *)nsel.p, (size_t)nf, st));
+    // segments: at most nf of them; the kernels read the real number from nsel
+    hipLaunchKernelGGL(k4_resolve_small, dim3((uint32_t)((nf + EXT_THREADS - 1) / EXT_THREADS)), dim3(EXT_THREADS), 0, st, d_units, q, (const uint64_t *)fkey,
+                       (const uint32_t *)fprev, nf, (const uint64_t *)segs, nseg, p_.xdrop, p_.hspthresh, group_table_device(), bigseg);
+    hipLaunchKernelGGL(k4_resolve_segments, dim3(1024), dim3(EXT_THREADS), 0, st, d_units, q, (const uint64_t *)fkey, (const uint32_t *)fprev, nf,
+                       (const uint64_t *)segs, nseg, (const uint64_t *)bigseg, p_.xdrop, p_.hspthresh, p_.transitions);
+    return 0;
+}
+
+// entropy and threshold; round trip 2: the HSP count (the resolution may have added candidates)
+int ExtBatch::entropy(ExtCounters *c) {
+    hipStream_t st = stream();
+    const UnitDesc *d_units = (const UnitDesc *)units.p;
+    hipLaunchKernelGGL(k4_entropy, dim3(1536), dim3(EXT_THREADS), 0, st, d_units, *q_, p_.hspthresh, p_.entropy, (mimeo_hsp *)hsps.p, (uint32_t *)hsp_unit.p);
+    hipLaunchKernelGGL(k4_entropy_big, dim3(128, 16), dim3(256), 0, st, d_units, *q_);
+    hipLaunchKernelGGL(k4_entropy_big_finish, dim3(16), dim3(256), 0, st, *q_, p_.hspthresh, p_.entropy, (mimeo_hsp *)hsps.p, (uint32_t *)hsp_unit.p);
+    HIP_TRY(hipEventRecord(ev[2], st));
+    HIP_TRY(hipMemcpyAsync(c, ctr.p, sizeof *c, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int ExtBatch::print_stats(const ExtCounters &c, uint64_t nf, uint64_t nm, bool over) {
+    if (sw_.k34_dbg & 8)
+        fprintf(stderr, "[k34] passed on because: left stop unproven %llu, right %llu, bound %llu, alarm %llu; ONLY alarm %llu, only left %llu, only right %llu, only bound %llu\n",
+                c.dbg[0], c.dbg[1], c.dbg[2], c.dbg[3], c.dbg[4], c.dbg[5], c.dbg[6], c.dbg[7]);
+    if (sw_.k4_stats && plan_ctr_ && nactive_) {
+        unsigned int pc[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpy(pc, plan_ctr_, 12, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[k34] split pass: %u tiles listed of %u, %u parts of ~131072 hits\n", pc[1], nactive_ * (unsigned)NTILE, pc[2]);
+    }
+    if (sw_.k4_stats)
+        fprintf(stderr, "[k4] units %u walk queue %llu walked %llu generic %llu long %llu followers %llu candidates %llu hsps %llu%s\n", (uint32_t)w_.size(),
+                c.nwalk_total, c.nwalked, (unsigned long long)nm, c.nlong, (unsigned long long)nf, c.ncand, c.nhsp, over ? "  (queue overflow: batch repeated)" : "");
+    return 0;
+}
+
+// An overflow: the queues grow to hold what the counters saw; what the batch showed goes into the sizing of the next ones
+// whatever happens to it now; and when the larger queues no longer fit the device the caller cuts the batch in two.
+// fullest, batch: the counters (they count beyond the capacities), with the followers and generic walks of the fullest shard / that times eight
+int ExtBatch::learn_and_grow(const queue_plan::Counts &fullest, const queue_plan::Counts &batch) {
+    queue_plan::grow(cap_, walk_cap_u_, fullest);
+    walk_entries_ = queue_plan::walk_entries(walk_cap_u_);
+    queue_plan::learn(boost, batch, expect_hits_, sw_.shrink);
+    uint64_t budget = 0;
+    const int rc = queue_budget(*this, &budget);
+    if (rc) return rc;
+    if (sw_.trace)
+        fprintf(stderr, "[trace] overflow of a batch of %u units: followers %llu (fullest shard), generic %llu, long %llu, cand %llu, walk %.2fx; queues would take %.2f GiB of %.2f GiB\n",
+                (uint32_t)w_.size(), (unsigned long long)fullest.followers, (unsigned long long)fullest.generic, (unsigned long long)fullest.nlong, (unsigned long long)fullest.ncand,
+                (double)fullest.nwalk_over / 1024.0, (double)queue_bytes() / (1 << 30), (double)budget / (1 << 30));
+    return queue_plan::must_split(splittable_, queue_bytes(), budget) ? MIMEO_ERR_SPLIT : 0;
 }
 
 int ExtBatch::finish(uint64_t *nhsp_out, ExtStats *stats) {
@@ -1138,147 +1158,37 @@ int ExtBatch::finish(uint64_t *nhsp_out, ExtStats *stats) {
     started_ = false;
     hipStream_t st = stream();
     const uint32_t nunits = (uint32_t)w_.size();
-    const mimeo_params *p = &p_;
-    const uint32_t *tab = group_table_device();
-    ExtQueues &q = *(ExtQueues *)q_;
-    const std::vector<UnitWork> &work = w_;
-    const std::vector<uint32_t> &h_selfs = h_selfs_;
-    const bool v1 = v1_;
-    const uint32_t key_bits = key_bits_;
-    const double expect_hits = expect_hits_;
-    const UnitDesc *d_units = (const UnitDesc *)units.p;
     int rc;
     ExtCounters c;
-    uint64_t nf_total = 0, nm_total = 0;
-    float ms_heavy = 0, ms_tails = 0, ms_walk = 0, ms_k34 = 0;
+    uint64_t nf = 0, nm = 0;
+    // try; if a queue overflowed: learn, grow, maybe split, enqueue again; at most four repeats
     for (int attempt = 0;; attempt++) {
-        uint64_t &cap_f = cap_f_, &cap_m = cap_m_, &cap_l = cap_l_, &cap_c = cap_c_;
-        HIP_TRY(hipStreamWaitEvent(st, ev[1], 0));   // the heavy phase may have run on another stream
-        // ---- tails, once per batch
-        HIP_TRY(hipEventRecord(ev[3], st));
-        hipLaunchKernelGGL(k4_extend_generic, dim3(generic_grid()), dim3(EXT_THREADS), 0, st, d_units, q, p->xdrop, p->hspthresh,
-                           p->transitions, tab);
-        if (!h_selfs.empty()) HIP_TRY(hipStreamWaitEvent(st, side_done, 0));
-        hipLaunchKernelGGL(k4_extend_long, dim3(768), dim3(EXT_THREADS), 0, st, d_units, q, p->xdrop, p->hspthresh, p->transitions);
-        HIP_TRY(hipMemcpyAsync(&c, ctr.p, sizeof c, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));   // round trip 1: follower count (sizes the sort), overflow check
-        uint64_t nf = 0, nm = 0, maxf = 0, maxm = 0;
-        for (int r = 0; r < 8; r++) {
-            nf += std::min<uint64_t>(c.nfollow8[r], cap_f);
-            nm += std::min<uint64_t>(c.nmed8[r], cap_m);
-            maxf = std::max<uint64_t>(maxf, c.nfollow8[r]);
-            maxm = std::max<uint64_t>(maxm, c.nmed8[r]);
+        if ((rc = tails(&c))) return rc;
+        uint64_t maxf = 0, maxm = 0;
+        nf = nm = 0;
+        for (int r = 0; r < queue_plan::SHARDS; r++) {
+            nf += std::min<uint64_t>(c.nfollow8[r], cap_.f); nm += std::min<uint64_t>(c.nmed8[r], cap_.m);
+            maxf = std::max<uint64_t>(maxf, c.nfollow8[r]); maxm = std::max<uint64_t>(maxm, c.nmed8[r]);
         }
-        nf_total = nf; nm_total = nm;
-        bool over = maxf > cap_f || maxm > cap_m || c.nlong > cap_l || c.ncand > cap_c || c.nwalk_over > 1024;
-        if (!over && nf) {
-            // the sort's second buffers, flags, segment lists and rocPRIM's scratch: slices of the second arena (~41 bytes per follower)
-            size_t t1 = 0, t2 = 0;
-            rocprim::counting_iterator<uint64_t> iota(0);
-            HIP_TRY(rocprim::radix_sort_pairs(nullptr, t1, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)nf, 0, key_bits, st));
-            HIP_TRY(rocprim::select(nullptr, t2, iota, (uint8_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nsel.p, (size_t)nf, st));
-            const size_t sz[6] = {nf * 8, nf * 4, nf, nf * 8, nf * 8, std::max(t1, t2) + 16};
-            size_t total = 0;
-            for (size_t z : sz) total += (z + 255) & ~(size_t)255;
-            if (total > arena_s.cap) {
-                for (DeviceBuf *d : {&fkey2, &fprev2, &flags, &segs, &bigseg, &tmp}) d->release();
-                size_t free_b = 0, total_b = 0;
-                HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-                size_t want = arena_s.cap ? total + total / 2 : total + total / 8;
-                if (want + (4ull << 30) > free_b + arena_s.cap) want = total;
-                if ((rc = arena_s.reserve(want)) && want > total) rc = arena_s.reserve(total);
-                if (rc) return rc == MIMEO_ERR_NOMEM && splittable_ ? MIMEO_ERR_SPLIT : rc;
-            }
-            size_t off = 0;
-            DeviceBuf *bufs[6] = {&fkey2, &fprev2, &flags, &segs, &bigseg, &tmp};
-            for (int i = 0; i < 6; i++) bufs[i]->set_view(carve(arena_s, &off, sz[i]), sz[i]);
-            // the eight shards gathered into fkey2 / fprev2; the sort writes back into the (now free) shard area
-            hipLaunchKernelGGL(k4_compact_followers, dim3(1024), dim3(256), 0, st, q, (uint64_t *)fkey2.p, (uint32_t *)fprev2.p);
-            HIP_TRY(rocprim::radix_sort_pairs(tmp.p, t1, (uint64_t *)fkey2.p, (uint64_t *)fkey.p, (uint32_t *)fprev2.p,
-                                              (uint32_t *)fprev.p, (size_t)nf, 0, key_bits, st));
-            hipLaunchKernelGGL(k4_segment_flags, dim3((uint32_t)((nf + 255) / 256)), dim3(256), 0, st, (const uint64_t *)fkey.p,
-                               (const uint32_t *)fprev.p, nf, q, (uint8_t *)flags.p);
-            HIP_TRY(rocprim::select(tmp.p, t2, iota, (uint8_t *)flags.p, (uint64_t *)segs.p, (uint64_t *)nsel.p, (size_t)nf, st));
-            // segments: at most nf of them; the kernels read the real number from nsel
-            hipLaunchKernelGGL(k4_resolve_small, dim3((uint32_t)((nf + EXT_THREADS - 1) / EXT_THREADS)), dim3(EXT_THREADS), 0, st,
-                               d_units, q, (const uint64_t *)fkey.p, (const uint32_t *)fprev.p, nf, (const uint64_t *)segs.p,
-                               (const uint64_t *)nsel.p, p->xdrop, p->hspthresh, tab, (uint64_t *)bigseg.p);
-            hipLaunchKernelGGL(k4_resolve_segments, dim3(1024), dim3(EXT_THREADS), 0, st, d_units, q, (const uint64_t *)fkey.p,
-                               (const uint32_t *)fprev.p, nf, (const uint64_t *)segs.p, (const uint64_t *)nsel.p,
-                               (const uint64_t *)bigseg.p, p->xdrop, p->hspthresh, p->transitions);
-        }
+        bool over = queue_plan::over(cap_, counts_of(c, maxf, maxm));
         if (!over) {
-            hipLaunchKernelGGL(k4_entropy, dim3(1536), dim3(EXT_THREADS), 0, st, d_units, q, p->hspthresh, p->entropy,
-                               (mimeo_hsp *)hsps.p, (uint32_t *)hsp_unit.p);
-            hipLaunchKernelGGL(k4_entropy_big, dim3(128, 16), dim3(256), 0, st, d_units, q);
-            hipLaunchKernelGGL(k4_entropy_big_finish, dim3(16), dim3(256), 0, st, q, p->hspthresh, p->entropy, (mimeo_hsp *)hsps.p,
-                               (uint32_t *)hsp_unit.p);
-            HIP_TRY(hipEventRecord(ev[2], st));
-            HIP_TRY(hipMemcpyAsync(&c, ctr.p, sizeof c, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));   // round trip 2: HSP count; the resolution may have added candidates
-            over = c.ncand > cap_c;
+            if ((nf && (rc = resolve_followers(nf))) || (rc = entropy(&c))) return rc;
+            over = c.ncand > cap_.c;
         }
         HIP_TRY(hipGetLastError());
-        if (k34_dbg_ & 8)
-            fprintf(stderr, "[k34] passed on because: left stop unproven %llu, right %llu, bound %llu, alarm %llu; ONLY alarm %llu, only left %llu, only right %llu, only bound %llu\n",
-                    c.dbg[0], c.dbg[1], c.dbg[2], c.dbg[3], c.dbg[4], c.dbg[5], c.dbg[6], c.dbg[7]);
-        if (k4_stats_ && plan_ctr_ && nactive_) {
-            unsigned int pc[3] = {0, 0, 0};
-            HIP_TRY(hipMemcpy(pc, plan_ctr_, 12, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[k34] split pass: %u tiles listed of %u, %u parts of ~131072 hits\n", pc[1], nactive_ * (unsigned)NTILE, pc[2]);
-        }
-        if (k4_stats_)
-            fprintf(stderr, "[k4] units %u walk queue %llu walked %llu generic %llu long %llu followers %llu candidates %llu hsps %llu%s\n", nunits,
-                    c.nwalk_total, c.nwalked, (unsigned long long)nm, c.nlong, (unsigned long long)nf, c.ncand, c.nhsp, over ? "  (queue overflow: batch repeated)" : "");
-        if (!over) {
-            float a = 0, b = 0, w = 0;
-            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-            HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
-            HIP_TRY(hipEventElapsedTime(&w, ev[1], ev[3]));
-            ms_heavy += a;
-            ms_tails += b;
-            ms_walk += w;
-            if (!v1 && nactive_) {
-                float t = 0;
-                HIP_TRY(hipEventElapsedTime(&t, kev[0], kev[1]));
-                ms_k34 += t;
-            }
-            break;
-        }
+        if ((rc = print_stats(c, nf, nm, over))) return rc;
+        if (!over) break;
         // (a walk queue that overflowed hides followers and candidates of the hits it dropped: the repeat may overflow those in turn)
         if (attempt >= 4) { set_error("extension queues overflowed four times in a row"); return MIMEO_ERR_LIMIT; }
-        // room for what the counters saw, and half as much again: the repeated tails may add candidates of their own
-        cap_f = std::max<uint64_t>(cap_f, maxf + maxf / 2 + 1024);
-        cap_m = std::max<uint64_t>(cap_m, maxm + maxm / 2 + 1024);
-        cap_l = std::max<uint64_t>(cap_l, c.nlong + c.nlong / 2 + 1024);
-        cap_c = std::max<uint64_t>(cap_c, 2 * c.ncand + 65536);
-        if (c.nwalk_over > 1024) {   // every unit's walk-queue region grows by what the fullest shard lacked, and a quarter
-            const double grow = 1.25 * (double)c.nwalk_over / 1024.0;
-            walk_entries_ = 0;
-            for (auto &w : walk_cap_u_) { if (w) w = (uint64_t)((double)w * grow) + 1024; walk_entries_ += 8 * w; }
-        }   // (boost_w learns from the batch's real share of walked hits at the end of finish(), whatever the capacities were)
         if (stats) stats->reruns++;
-        // what this batch showed goes into the sizing of the next ones whatever happens to it now
-        if (expect_hits > 1e6) {
-            boost_f = std::min(4096.0, std::max(boost_f, 1.5 * (double)(8 * maxf) / (0.02 * expect_hits)));
-            boost_m = std::min(4096.0, std::max(boost_m, 1.5 * (double)(8 * maxm) / (0.03 * expect_hits)));
-            boost_l = std::min(4096.0, std::max(boost_l, 1.5 * (double)c.nlong / (0.002 * expect_hits)));
-            boost_c = std::min(4096.0, std::max(boost_c, 1.5 * (double)c.ncand / (0.002 * expect_hits)));
-            boost_w = std::min(4096.0, std::max(boost_w, 1.5 * (double)c.nwalk_total / (0.08 * expect_hits)));   // the counters count beyond the capacities
-            // ... and the fullest shard of the worst unit, not the batch's average, is what has to fit (microsatellites are not
-            // spread evenly over the pairs); shrink_ (tests) made the capacities smaller, not the need larger
-            boost_w = std::min(4096.0, std::max(boost_w, 1.5 * boost_w * ((double)c.nwalk_over / 1024.0) / shrink_));
-        }
-        {
-            uint64_t budget = 0;
-            if ((rc = queue_budget(*this, &budget))) return rc;
-            if (getenv("MIMEO_TRACE"))
-                fprintf(stderr, "[trace] overflow of a batch of %u units: followers %llu (fullest shard), generic %llu, long %llu, cand %llu, walk %.2fx; queues would take %.2f GiB of %.2f GiB\n",
-                        nunits, (unsigned long long)maxf, (unsigned long long)maxm, c.nlong, c.ncand, (double)c.nwalk_over / 1024.0, (double)queue_bytes() / (1 << 30), (double)budget / (1 << 30));
-            if (splittable_ && queue_bytes() > budget) return MIMEO_ERR_SPLIT;   // the caller cuts the batch in two
-        }
+        if ((rc = learn_and_grow(counts_of(c, maxf, maxm), counts_of(c, queue_plan::SHARDS * maxf, queue_plan::SHARDS * maxm)))) return rc;
         if ((rc = enqueue_heavy())) return rc;   // the batch again, on this stream, with room
     }
+    float ms_heavy = 0, ms_tails = 0, ms_walk = 0, ms_k34 = 0;
+    HIP_TRY(hipEventElapsedTime(&ms_heavy, ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms_tails, ev[1], ev[2]));
+    HIP_TRY(hipEventElapsedTime(&ms_walk, ev[1], ev[3]));
+    if (!sw_.v1 && nactive_) HIP_TRY(hipEventElapsedTime(&ms_k34, ev[4], ev[5]));
     uint64_t nhsp = c.nhsp;
     if (!mirror_dst_.empty() && nhsp) {   // shared plus strand: the mirror units receive their (transposed) HSPs
         unsigned long long *mctr = (unsigned long long *)((char *)mirror.p + (size_t)nunits * 4 + (8 - ((size_t)nunits * 4) % 8) % 8);
@@ -1293,37 +1203,25 @@ int ExtBatch::finish(uint64_t *nhsp_out, ExtStats *stats) {
     h_unit_hits.resize(nunits);
     HIP_TRY(hipMemcpy(h_unit_hits.data(), unit_hits.p, (size_t)nunits * 8, hipMemcpyDeviceToHost));
     *nhsp_out = nhsp;
-    if (expect_hits > 1e6) {
-        const double e = expect_hits;
-        boost_f = std::min(4096.0, std::max(boost_f, 1.5 * (double)nf_total / (0.02 * e)));
-        boost_m = std::min(4096.0, std::max(boost_m, 1.5 * (double)nm_total / (0.03 * e)));
-        boost_l = std::min(4096.0, std::max(boost_l, 1.5 * (double)c.nlong / (0.002 * e)));
-        boost_c = std::min(4096.0, std::max(boost_c, 1.5 * (double)c.ncand / (0.002 * e)));
-        boost_w = std::min(4096.0, std::max(boost_w, 1.5 * (double)c.nwalk_total / (0.08 * e)));
-        boost_w = std::min(4096.0, std::max(boost_w, 1.5 * boost_w * ((double)c.nwalk_over / 1024.0) / shrink_));   // the fullest shard of the worst unit
-    }
+    queue_plan::learn(boost, counts_of(c, nf, nm), expect_hits_, sw_.shrink);   // a batch that fitted teaches too
     if (stats) {
         for (uint32_t u = 0; u < nunits; u++) {
-            if (!(work[u].ti.n && work[u].qi.n)) continue;   // a mirror unit's seed scan is never run: it counts no hits and no bytes
+            const UnitWork &w = w_[u];
+            if (!(w.ti.n && w.qi.n)) continue;   // a mirror unit's seed scan is never run: it counts no hits and no bytes
             stats->seed_hits += h_unit_hits[u];
-            const uint64_t Lq = work[u].d.Q.len, H = h_unit_hits[u];
+            const uint64_t Lq = w.d.Q.len, H = h_unit_hits[u];
             // B_scan = ceil(Lq/4) + 8*W*(Lq-18) + 4*H + 8*H, W = 13
             stats->scan_bytes_algorithmic += (Lq + 3) / 4 + (Lq > 18 ? 8ull * 13ull * (Lq - 18) : 0) + 12ull * H;
             // compulsory traffic of the fused kernel: both offset arrays, positions and frames of both sides once
-            stats->scan_bytes_kernel += 2ull * 4ull * ((uint64_t)NBUCKET + 1) + 52ull * ((uint64_t)work[u].ti.n + work[u].qi.n);
+            stats->scan_bytes_kernel += 2ull * 4ull * ((uint64_t)NBUCKET + 1) + 52ull * ((uint64_t)w.ti.n + w.qi.n);
             stats->heavy_launches++;   // units: the seed-scan kernel takes a batch of them per launch
         }
-        if (!v1 && nactive_) stats->heavy_kernel_launches++;
-        stats->walked += c.nwalked;
-        stats->walk_queue += c.nwalk_total;
-        stats->ms_walk += ms_walk;
-        stats->ms_k34 += v1 ? ms_heavy : ms_k34;
-        stats->followers += nf_total;
-        stats->candidates += c.ncand;
-        stats->ms_heavy += ms_heavy;
-        stats->ms_tails += ms_tails;
+        if (!sw_.v1 && nactive_) stats->heavy_kernel_launches++;
+        stats->walked += c.nwalked; stats->walk_queue += c.nwalk_total; stats->followers += nf; stats->candidates += c.ncand;
+        stats->ms_heavy += ms_heavy; stats->ms_tails += ms_tails; stats->ms_walk += ms_walk; stats->ms_k34 += sw_.v1 ? ms_heavy : ms_k34;
     }
     return 0;
 }
 
 }  // namespace mimeo
+
