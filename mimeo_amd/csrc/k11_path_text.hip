@@ -24,7 +24,9 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "device_util.h"
+#include <memory>
+
+#include "path_call.h"
 #include "path_text_host.h"
 
 namespace mimeo {
@@ -54,19 +56,16 @@ __global__ __launch_bounds__(256) void k11_path_text(const StrandView *__restric
                                                      const uint64_t *__restrict__ bcol, const uint64_t *__restrict__ rowoff, uint32_t lead,
                                                      const Job *__restrict__ jobs, uint32_t njobs, uint8_t *__restrict__ trow,
                                                      uint8_t *__restrict__ qrow) {
-    const uint32_t jid = __builtin_amdgcn_readfirstlane((blockIdx.x * 256u + threadIdx.x) >> 6);   // wave-uniform
-    if (jid >= njobs) return;
-    const Job job = jobs[jid];
-    const uint32_t lane = threadIdx.x & 63u;
-    const mimeo_alignment a = aln[job.aln];
-    // the strand views come out of a device table: into global address space once per wavefront (device_util.h)
-    const GStrandView T(t_fwd[a.tid]), Q((a.qstrand ? q_rc : q_fwd)[a.qid]);
-    const uint64_t b0 = first[job.aln] - first[0], b1 = first[job.aln + 1] - first[0];   // the slice's blocks start at first[0]
+    PathJob<Job> J;
+    if (!J.load(t_fwd, q_fwd, q_rc, aln, first, jobs, njobs)) return;
+    const Job job = J.job;
+    const GStrandView &T = J.T, &Q = J.Q;
+    const uint64_t b0 = J.b0, b1 = J.b1;
     // byte of the row buffers that holds column 0 of this row: the slice's rows lie as in the output arrays, behind `lead`
     // bytes that give the buffers the output's alignment mod 16
     const uint64_t o = lead + (rowoff[job.aln] - rowoff[0]);
     const uint64_t lo = o + job.c0, hi = o + job.c1;   // the job's bytes; lo < hi, and b0 < b1: a row with columns has blocks
-    for (uint64_t g = (lo >> 4) + lane; g < ((hi + 15u) >> 4); g += 64) {
+    for (uint64_t g = (lo >> 4) + J.lane; g < ((hi + 15u) >> 4); g += 64) {
         const uint64_t gs = g << 4;
         // the bytes [va, vb) of the group belong to the job: all 16, except at a row's head and tail
         const uint32_t va = gs < lo ? (uint32_t)(lo - gs) : 0u, vb = gs + 16u > hi ? (uint32_t)(hi - gs) : 16u;
@@ -146,109 +145,59 @@ static_assert(sizeof(Job) == 24 && sizeof(mimeo_path_block) == 12, "layouts the 
 // slice of its own); MIMEO_PATH_TEXT_SPLIT_COLUMNS: a row of more columns than this is cut into jobs of this many (default
 // 16384; 0: never); MIMEO_PATH_TEXT_STATS: what the call did and the HIP-event time of its kernels, on stderr.  Results depend
 // on none of them.
-static uint64_t env_u64(const char *name, uint64_t dflt) {
-    const char *s = getenv(name);
-    if (!s || !*s) return dflt;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(s, &end, 10);
-    return end && *end == 0 ? (uint64_t)v : dflt;
-}
-
 int path_text_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
                      const mimeo_path_block *blocks, uint64_t nblocks, uint64_t **row_first_out, uint8_t **trow_out, uint8_t **qrow_out) {
     // every check on the host, before anything is uploaded: a bad path never reaches the kernel
-    std::vector<uint64_t> len_t(T->scaf.size()), len_q(Q->scaf.size());
-    for (size_t i = 0; i < len_t.size(); i++) len_t[i] = T->scaf[i].len;
-    for (size_t i = 0; i < len_q.size(); i++) len_q[i] = Q->scaf[i].len;
     std::string msg;
-    if (!path_text_host::validate(len_t, len_q, aln, n, first, blocks, nblocks, &msg)) { set_error(msg); return MIMEO_ERR_ARG; }
-    uint64_t *row_first = (uint64_t *)malloc((n + 1) * sizeof(uint64_t));
+    if (!path_text_host::validate(scaffold_lengths(T), scaffold_lengths(Q), aln, n, first, blocks, nblocks, &msg)) { set_error(msg); return MIMEO_ERR_ARG; }
+    // the three arrays of the result: freed on every way out but the last line, which hands them to the caller
+    std::unique_ptr<uint64_t, decltype(&free)> row_first((uint64_t *)malloc((n + 1) * sizeof(uint64_t)), &free);
     if (!row_first) { set_error("mimeo_path_text: out of host memory"); return MIMEO_ERR_NOMEM; }
-    path_text_host::row_first_of(first, blocks, n, row_first);
-    const uint64_t total = row_first[n];
-    uint8_t *h_t = total ? (uint8_t *)malloc(total) : nullptr, *h_q = total ? (uint8_t *)malloc(total) : nullptr;
-    if (total && (!h_t || !h_q)) {
-        free(row_first); free(h_t); free(h_q);
-        set_error("mimeo_path_text: out of host memory for the rows");
-        return MIMEO_ERR_NOMEM;
-    }
+    path_text_host::row_first_of(first, blocks, n, row_first.get());
+    const uint64_t total = row_first.get()[n];
+    std::unique_ptr<uint8_t, decltype(&free)> h_t(total ? (uint8_t *)malloc(total) : nullptr, &free), h_q(total ? (uint8_t *)malloc(total) : nullptr, &free);
+    if (total && (!h_t || !h_q)) { set_error("mimeo_path_text: out of host memory for the rows"); return MIMEO_ERR_NOMEM; }
     const uint64_t slice_columns = std::max<uint64_t>(1, env_u64("MIMEO_PATH_TEXT_SLICE_COLUMNS", path_text_host::DEFAULT_SLICE_COLUMNS));
     const uint64_t split_columns = env_u64("MIMEO_PATH_TEXT_SPLIT_COLUMNS", path_text_host::DEFAULT_SPLIT_COLUMNS);
-    const bool stats = getenv("MIMEO_PATH_TEXT_STATS") != nullptr;
-    hipStream_t st = stream();
-    std::vector<StrandView> vt(len_t.size()), vqf(len_q.size()), vqr(len_q.size());
-    for (size_t i = 0; i < vt.size(); i++) vt[i] = T->scaf[i].fwd.view(false);
-    for (size_t i = 0; i < vqf.size(); i++) { vqf[i] = Q->scaf[i].fwd.view(false); vqr[i] = Q->scaf[i].rc.view(false); }
-    DeviceBuf dvt, dvqf, dvqr, da, df, db, dc, dr, dj, dtrow, dqrow;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    auto done = [&](int r) {
-        for (DeviceBuf *b : {&dvt, &dvqf, &dvqr, &da, &df, &db, &dc, &dr, &dj, &dtrow, &dqrow}) b->release();
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (r) { free(row_first); free(h_t); free(h_q); }
-        else { *row_first_out = row_first; *trow_out = h_t; *qrow_out = h_q; }
-        return r;
-    };
-#define K11_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return done(hip_fail(e__, #call, __FILE__, __LINE__)); } while (0)
-    if (!total) return done(0);   // no column anywhere: nothing to launch
-    int rc;
-    if ((rc = dvt.reserve(vt.size() * sizeof(StrandView) + 16)) || (rc = dvqf.reserve(vqf.size() * sizeof(StrandView) + 16)) ||
-        (rc = dvqr.reserve(vqr.size() * sizeof(StrandView) + 16)))
-        return done(rc);
-    K11_TRY(hipMemcpyAsync(dvt.p, vt.data(), vt.size() * sizeof(StrandView), hipMemcpyHostToDevice, st));
-    K11_TRY(hipMemcpyAsync(dvqf.p, vqf.data(), vqf.size() * sizeof(StrandView), hipMemcpyHostToDevice, st));
-    K11_TRY(hipMemcpyAsync(dvqr.p, vqr.data(), vqr.size() * sizeof(StrandView), hipMemcpyHostToDevice, st));
-    if (stats) { K11_TRY(hipEventCreate(&ev[0])); K11_TRY(hipEventCreate(&ev[1])); }
-    const auto slices = path_text_host::plan_slices(row_first, first, n, path_text_host::SLICE_RECORDS, path_text_host::SLICE_BLOCKS, slice_columns);
-    std::vector<Job> jobs;
+    std::vector<Job> jobs;   // in front of the call: what it copies from outlives it
     std::vector<uint64_t> bcol;
+    PathCall pc(getenv("MIMEO_PATH_TEXT_STATS") != nullptr);
+    DeviceBuf &dc = pc.buf(), &dr = pc.buf(), &dtrow = pc.buf(), &dqrow = pc.buf();
+    int rc;
+    if (total && (rc = pc.views(T, Q))) return rc;   // no column anywhere: nothing to launch
+    const auto slices = path_text_host::plan_slices(row_first.get(), first, n, path_text_host::SLICE_RECORDS, path_text_host::SLICE_BLOCKS, slice_columns);
     uint64_t njobs_all = 0, nslices = 0;
-    double ms_kernel = 0;
-    const uint32_t launch_jobs = 1u << 22;   // jobs per launch: the kernel numbers them in 32 bits
     for (const auto &s : slices) {
-        const uint64_t a0 = s.first, na = s.second - s.first, k0 = first[a0], nb = first[s.second] - k0;
-        const uint64_t cols = row_first[s.second] - row_first[a0];
+        const uint64_t a0 = s.first, na = s.second - s.first, nb = first[s.second] - first[a0];
+        const uint64_t col0 = row_first.get()[a0], cols = row_first.get()[s.second] - col0;
         if (!cols) continue;   // a slice of alignments without columns
-        const uint32_t lead = (uint32_t)(row_first[a0] & 15u);
-        path_text_host::plan_jobs(row_first, a0, s.second, split_columns, jobs);
+        const uint32_t lead = (uint32_t)(col0 & 15u);
+        path_text_host::plan_jobs(row_first.get(), a0, s.second, split_columns, jobs);
         path_text_host::block_columns(first, blocks, a0, s.second, bcol);
         const size_t row_bytes = (size_t)(((lead + cols + 15u) & ~15ull) + 16u);
-        if ((rc = da.reserve(na * sizeof(mimeo_alignment))) || (rc = df.reserve((na + 1) * 8)) || (rc = dr.reserve((na + 1) * 8)) ||
-            (rc = db.reserve(nb * sizeof(mimeo_path_block) + 16)) || (rc = dc.reserve(nb * 8 + 16)) || (rc = dj.reserve(jobs.size() * sizeof(Job))) ||
+        if ((rc = pc.slice(aln, first, blocks, a0, s.second)) || (rc = dr.reserve((na + 1) * 8)) || (rc = dc.reserve(nb * 8 + 16)) ||
             (rc = dtrow.reserve(row_bytes)) || (rc = dqrow.reserve(row_bytes)))
-            return done(rc);
-        // the stream orders a slice's copies behind the launch that read the slice before
-        K11_TRY(hipMemcpyAsync(da.p, aln + a0, na * sizeof(mimeo_alignment), hipMemcpyHostToDevice, st));
-        K11_TRY(hipMemcpyAsync(df.p, first + a0, (na + 1) * 8, hipMemcpyHostToDevice, st));
-        K11_TRY(hipMemcpyAsync(dr.p, row_first + a0, (na + 1) * 8, hipMemcpyHostToDevice, st));
-        K11_TRY(hipMemcpyAsync(db.p, blocks + k0, nb * sizeof(mimeo_path_block), hipMemcpyHostToDevice, st));
-        K11_TRY(hipMemcpyAsync(dc.p, bcol.data(), nb * 8, hipMemcpyHostToDevice, st));
-        K11_TRY(hipMemcpyAsync(dj.p, jobs.data(), jobs.size() * sizeof(Job), hipMemcpyHostToDevice, st));
-        K11_TRY(hipStreamSynchronize(st));   // `jobs` and `bcol` are rebuilt for the next slice
-        if (stats) K11_TRY(hipEventRecord(ev[0], st));
-        for (uint64_t j0 = 0; j0 < jobs.size(); j0 += launch_jobs) {
-            const uint32_t nj = (uint32_t)std::min<uint64_t>(launch_jobs, jobs.size() - j0);
-            hipLaunchKernelGGL(k11_path_text, dim3((nj + 3) / 4), dim3(256), 0, st, (const StrandView *)dvt.p, (const StrandView *)dvqf.p,
-                               (const StrandView *)dvqr.p, (const mimeo_alignment *)da.p, (const uint64_t *)df.p, (const mimeo_path_block *)db.p,
-                               (const uint64_t *)dc.p, (const uint64_t *)dr.p, lead, (const Job *)dj.p + j0, nj, (uint8_t *)dtrow.p, (uint8_t *)dqrow.p);
-            K11_TRY(hipGetLastError());
-        }
-        if (stats) K11_TRY(hipEventRecord(ev[1], st));
-        K11_TRY(hipMemcpyAsync(h_t + row_first[a0], (const uint8_t *)dtrow.p + lead, cols, hipMemcpyDeviceToHost, st));
-        K11_TRY(hipMemcpyAsync(h_q + row_first[a0], (const uint8_t *)dqrow.p + lead, cols, hipMemcpyDeviceToHost, st));
-        K11_TRY(hipStreamSynchronize(st));
+            return rc;
+        HIP_TRY(hipMemcpyAsync(dr.p, row_first.get() + a0, (na + 1) * 8, hipMemcpyHostToDevice, pc.st));
+        HIP_TRY(hipMemcpyAsync(dc.p, bcol.data(), nb * 8, hipMemcpyHostToDevice, pc.st));
+        rc = pc.run(jobs, 4, [&](const Job *d_jobs, uint32_t nj, dim3 grid) {
+            hipLaunchKernelGGL(k11_path_text, grid, dim3(256), 0, pc.st, pc.t_fwd(), pc.q_fwd(), pc.q_rc(), pc.aln(), pc.first(), pc.blocks(),
+                               (const uint64_t *)dc.p, (const uint64_t *)dr.p, lead, d_jobs, nj, (uint8_t *)dtrow.p, (uint8_t *)dqrow.p);
+        });
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(h_t.get() + col0, (const uint8_t *)dtrow.p + lead, cols, hipMemcpyDeviceToHost, pc.st));
+        HIP_TRY(hipMemcpyAsync(h_q.get() + col0, (const uint8_t *)dqrow.p + lead, cols, hipMemcpyDeviceToHost, pc.st));
+        HIP_TRY(hipStreamSynchronize(pc.st));   // the rows are here, and `jobs` and `bcol` may be rebuilt for the next slice
         nslices++;
-        if (stats) {
-            float ms = 0;
-            K11_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            ms_kernel += ms;
-            njobs_all += jobs.size();
-        }
+        njobs_all += jobs.size();
     }
-#undef K11_TRY
-    if (stats)
+    if (pc.stats && total)   // a call without columns has launched nothing and says nothing
         fprintf(stderr, "[k11] path text: %llu alignments, %llu columns, %llu jobs, slices %llu, kernels %.3f ms\n", (unsigned long long)n,
-                (unsigned long long)total, (unsigned long long)njobs_all, (unsigned long long)nslices, ms_kernel);
-    return done(0);
+                (unsigned long long)total, (unsigned long long)njobs_all, (unsigned long long)nslices, pc.ms_kernel);
+    *row_first_out = row_first.release();
+    *trow_out = h_t.release();
+    *qrow_out = h_q.release();
+    return 0;
 }
 
 }  // namespace mimeo

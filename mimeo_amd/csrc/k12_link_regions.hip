@@ -22,8 +22,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "common.h"
 #include "link_regions_host.h"
+#include "path_call.h"
 
 namespace mimeo {
 
@@ -66,20 +66,13 @@ __global__ __launch_bounds__(256) void k12_link_regions(const mimeo_alignment *_
     const uint64_t b0 = first[job.aln] - first[0], b1 = first[job.aln + 1] - first[0];   // the slice's blocks start at first[0]; b1 > b0 (host)
     const uint32_t w0 = job.w0, w1 = job.w1;                                              // w0 < w1 (rule A, host)
     // B: the first block that ends behind w0 ...
-    uint64_t lo = b0, hi = b1;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        const mimeo_path_block b = blocks[mid];
-        if (b.t + b.len > w0) hi = mid; else lo = mid + 1;   // t + len <= the scaffold's length: no wrap in 32 bits
-    }
-    if (lo == b1) return;   // the window lies behind the alignment
-    const uint64_t ks = lo;
+    const uint64_t ks = first_block_ending_behind(blocks, b0, b1, w0);
+    if (ks == b1) return;   // the window lies behind the alignment
     const mimeo_path_block bs = blocks[ks];
     const uint32_t s = max(bs.t, w0);
     if (s >= w1) return;    // ... starts behind the window: the window lies in a deletion, or in front of the alignment
     // ... and the last block that starts in front of w1: block ks does
-    lo = ks;
-    hi = b1 - 1;
+    uint64_t lo = ks, hi = b1 - 1;
     while (lo < hi) {
         const uint64_t mid = (lo + hi + 1) >> 1;
         if (blocks[mid].t < w1) lo = mid; else hi = mid - 1;
@@ -134,20 +127,11 @@ static_assert(sizeof(mimeo_interval) == 12 && sizeof(mimeo_window_item) == 16 &&
 
 // MIMEO_LINK_SLICE_BLOCKS: blocks per slice (default 2^24, as K9 and K10; 1: every alignment a slice of its own);
 // MIMEO_LINK_STATS: what the call did and the HIP-event time of its kernels, on stderr.  Results depend on neither.
-static uint64_t env_u64(const char *name, uint64_t dflt) {
-    const char *s = getenv(name);
-    if (!s || !*s) return dflt;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(s, &end, 10);
-    return end && *end == 0 ? (uint64_t)v : dflt;
-}
-
 int link_regions_device(const mimeo_genome *T, const mimeo_alignment *aln, uint64_t n, const uint64_t *first, const mimeo_path_block *blocks,
                         uint64_t nblocks, const mimeo_interval *regions, uint64_t nreg, const uint32_t *chrom_of_scaf, const mimeo_window_item *items,
                         uint64_t nitems, uint32_t min_cover_pct, uint32_t *family, uint64_t *links) {
     // every check on the host, before anything is uploaded: no bad path, region or item reaches the kernel
-    std::vector<uint64_t> len_t(T->scaf.size());
-    for (size_t i = 0; i < len_t.size(); i++) len_t[i] = T->scaf[i].len;
+    const std::vector<uint64_t> len_t = scaffold_lengths(T);
     std::string msg;
     std::vector<uint32_t> chrom;
     if (!link_regions_host::validate(len_t, aln, n, first, blocks, nblocks, regions, nreg, chrom_of_scaf, items, nitems, min_cover_pct, chrom, &msg)) {
@@ -156,92 +140,51 @@ int link_regions_device(const mimeo_genome *T, const mimeo_alignment *aln, uint6
     }
     const uint64_t slice_blocks = std::max<uint64_t>(1, env_u64("MIMEO_LINK_SLICE_BLOCKS", 1ull << 24));
     const uint64_t slice_records = 1ull << 22;
-    const uint64_t launch_jobs = 1ull << 22;   // jobs per launch: 64 MiB of jobs
-    const bool stats = getenv("MIMEO_LINK_STATS") != nullptr;
-    hipStream_t st = stream();
     const std::vector<uint32_t> chrom_first = link_regions_host::chrom_offsets(regions, nreg, chrom.size());
-    std::vector<uint32_t> scaf_len(len_t.size());
-    for (size_t i = 0; i < len_t.size(); i++) scaf_len[i] = (uint32_t)len_t[i];   // scaffolds are below 2^31 bases
-    DeviceBuf dreg, dcf, dcs, dsl, dpar, dfam, dlnk, da, df, db, dj;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    auto done = [&](int r) {
-        for (DeviceBuf *b : {&dreg, &dcf, &dcs, &dsl, &dpar, &dfam, &dlnk, &da, &df, &db, &dj}) b->release();
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        return r;
-    };
-#define K12_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return done(hip_fail(e__, #call, __FILE__, __LINE__)); } while (0)
+    const std::vector<uint32_t> scaf_len(len_t.begin(), len_t.end());   // scaffolds are below 2^31 bases
+    std::vector<Job> jobs;   // in front of the call: what it copies from outlives it
+    PathCall pc(getenv("MIMEO_LINK_STATS") != nullptr);
+    DeviceBuf &dreg = pc.buf(), &dcf = pc.buf(), &dcs = pc.buf(), &dsl = pc.buf(), &dpar = pc.buf(), &dfam = pc.buf(), &dlnk = pc.buf();
     int rc;
     if ((rc = dreg.reserve(nreg * sizeof(mimeo_interval) + 16)) || (rc = dcf.reserve(chrom_first.size() * 4)) || (rc = dcs.reserve(chrom.size() * 4 + 16)) ||
         (rc = dsl.reserve(scaf_len.size() * 4 + 16)) || (rc = dpar.reserve(nreg * 4)) || (rc = dfam.reserve(nreg * 4)) || (rc = dlnk.reserve(nreg * 8)))
-        return done(rc);
-    K12_TRY(hipMemcpyAsync(dreg.p, regions, nreg * sizeof(mimeo_interval), hipMemcpyHostToDevice, st));
-    K12_TRY(hipMemcpyAsync(dcf.p, chrom_first.data(), chrom_first.size() * 4, hipMemcpyHostToDevice, st));
-    K12_TRY(hipMemcpyAsync(dcs.p, chrom.data(), chrom.size() * 4, hipMemcpyHostToDevice, st));
-    K12_TRY(hipMemcpyAsync(dsl.p, scaf_len.data(), scaf_len.size() * 4, hipMemcpyHostToDevice, st));
-    K12_TRY(hipMemsetAsync(dlnk.p, 0, nreg * 8, st));   // once per call: every job adds to it
-    const uint32_t reg_blocks = (uint32_t)((nreg + 255) / 256);
-    if (stats) { K12_TRY(hipEventCreate(&ev[0])); K12_TRY(hipEventCreate(&ev[1])); }
-    double ms_kernel = 0;
-    uint64_t launches = 0;
-    auto timed = [&](bool begin) -> hipError_t {   // HIP events around a kernel, only when the statistics are asked for
-        if (!stats) return hipSuccess;
-        if (begin) return hipEventRecord(ev[0], st);
-        hipError_t e = hipEventRecord(ev[1], st);
-        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        ms_kernel += ms;
-        launches++;
-        return e;
-    };
-    K12_TRY(timed(true));
-    hipLaunchKernelGGL(k12_init, dim3(reg_blocks), dim3(256), 0, st, (uint32_t *)dpar.p, (uint32_t)nreg);
-    K12_TRY(hipGetLastError());
-    K12_TRY(timed(false));
+        return rc;
+    HIP_TRY(hipMemcpyAsync(dreg.p, regions, nreg * sizeof(mimeo_interval), hipMemcpyHostToDevice, pc.st));
+    HIP_TRY(hipMemcpyAsync(dcf.p, chrom_first.data(), chrom_first.size() * 4, hipMemcpyHostToDevice, pc.st));
+    HIP_TRY(hipMemcpyAsync(dcs.p, chrom.data(), chrom.size() * 4, hipMemcpyHostToDevice, pc.st));
+    HIP_TRY(hipMemcpyAsync(dsl.p, scaf_len.data(), scaf_len.size() * 4, hipMemcpyHostToDevice, pc.st));
+    HIP_TRY(hipMemsetAsync(dlnk.p, 0, nreg * 8, pc.st));   // once per call: every job adds to it
+    const dim3 reg_grid((uint32_t)((nreg + 255) / 256));
+    if ((rc = pc.timed([&] { hipLaunchKernelGGL(k12_init, reg_grid, dim3(256), 0, pc.st, (uint32_t *)dpar.p, (uint32_t)nreg); }))) return rc;
     const auto slices = path_stats_host::plan_slices(first, n, slice_records, slice_blocks);
     std::vector<uint64_t> order, start;
     window_stats_host::bucket_items(slices, items, nitems, order, start);
-    std::vector<Job> jobs;
     uint64_t njobs_all = 0, slices_used = 0;
     for (size_t si = 0; si < slices.size(); si++) {
         if (start[si] == start[si + 1]) continue;   // no item asks for this slice: nothing of it is uploaded
-        const uint64_t a0 = slices[si].first, na = slices[si].second - a0, k0 = first[a0], nb = first[slices[si].second] - k0;
-        link_regions_host::plan_jobs(first, a0, regions, items, order.data(), start[si], start[si + 1], min_cover_pct, jobs);
+        link_regions_host::plan_jobs(first, slices[si].first, regions, items, order.data(), start[si], start[si + 1], min_cover_pct, jobs);
         if (jobs.empty()) continue;
         slices_used++;
-        if ((rc = da.reserve(na * sizeof(mimeo_alignment))) || (rc = df.reserve((na + 1) * 8)) || (rc = db.reserve(nb * sizeof(mimeo_path_block) + 16)) ||
-            (rc = dj.reserve(std::min<uint64_t>(jobs.size(), launch_jobs) * sizeof(Job))))
-            return done(rc);
-        // the stream orders a slice's copies behind the launch that read the slice before
-        K12_TRY(hipMemcpyAsync(da.p, aln + a0, na * sizeof(mimeo_alignment), hipMemcpyHostToDevice, st));
-        K12_TRY(hipMemcpyAsync(df.p, first + a0, (na + 1) * 8, hipMemcpyHostToDevice, st));
-        K12_TRY(hipMemcpyAsync(db.p, blocks + k0, nb * sizeof(mimeo_path_block), hipMemcpyHostToDevice, st));   // nb >= 1: a job's alignment has blocks
-        for (uint64_t j0 = 0; j0 < jobs.size(); j0 += launch_jobs) {
-            const uint64_t nj = std::min<uint64_t>(launch_jobs, jobs.size() - j0);
-            K12_TRY(hipMemcpyAsync(dj.p, jobs.data() + j0, nj * sizeof(Job), hipMemcpyHostToDevice, st));
-            K12_TRY(timed(true));
-            hipLaunchKernelGGL(k12_link_regions, dim3((uint32_t)((nj + 255) / 256)), dim3(256), 0, st, (const mimeo_alignment *)da.p, (const uint64_t *)df.p,
-                               (const mimeo_path_block *)db.p, (const Job *)dj.p, (uint32_t)nj, (const mimeo_interval *)dreg.p, (const uint32_t *)dcf.p,
-                               (const uint32_t *)dcs.p, (const uint32_t *)dsl.p, min_cover_pct, (uint32_t *)dpar.p, (unsigned long long *)dlnk.p);
-            K12_TRY(hipGetLastError());
-            K12_TRY(timed(false));
-        }
-        K12_TRY(hipStreamSynchronize(st));   // `jobs` is rebuilt for the next slice
+        if ((rc = pc.slice(aln, first, blocks, slices[si].first, slices[si].second))) return rc;
+        rc = pc.run(jobs, 256, [&](const Job *d_jobs, uint32_t nj, dim3 grid) {   // one lane per job
+            hipLaunchKernelGGL(k12_link_regions, grid, dim3(256), 0, pc.st, pc.aln(), pc.first(), pc.blocks(), d_jobs, nj, (const mimeo_interval *)dreg.p,
+                               (const uint32_t *)dcf.p, (const uint32_t *)dcs.p, (const uint32_t *)dsl.p, min_cover_pct, (uint32_t *)dpar.p,
+                               (unsigned long long *)dlnk.p);
+        });
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(pc.st));   // `jobs` is rebuilt for the next slice
         njobs_all += jobs.size();
     }
-    K12_TRY(timed(true));
-    hipLaunchKernelGGL(k12_flatten, dim3(reg_blocks), dim3(256), 0, st, (const uint32_t *)dpar.p, (uint32_t)nreg, (uint32_t *)dfam.p);
-    K12_TRY(hipGetLastError());
-    K12_TRY(timed(false));
-    K12_TRY(hipMemcpyAsync(family, dfam.p, nreg * 4, hipMemcpyDeviceToHost, st));
-    K12_TRY(hipMemcpyAsync(links, dlnk.p, nreg * 8, hipMemcpyDeviceToHost, st));
-    K12_TRY(hipStreamSynchronize(st));
-#undef K12_TRY
-    if (stats)
+    rc = pc.timed([&] { hipLaunchKernelGGL(k12_flatten, reg_grid, dim3(256), 0, pc.st, (const uint32_t *)dpar.p, (uint32_t)nreg, (uint32_t *)dfam.p); });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(family, dfam.p, nreg * 4, hipMemcpyDeviceToHost, pc.st));
+    HIP_TRY(hipMemcpyAsync(links, dlnk.p, nreg * 8, hipMemcpyDeviceToHost, pc.st));
+    HIP_TRY(hipStreamSynchronize(pc.st));
+    if (pc.stats)
         fprintf(stderr, "[k12] link regions: %llu items, %llu regions, %llu jobs, slices %llu of %zu, launches %llu, kernels %.3f ms\n",
                 (unsigned long long)nitems, (unsigned long long)nreg, (unsigned long long)njobs_all, (unsigned long long)slices_used, slices.size(),
-                (unsigned long long)launches, ms_kernel);
-    return done(0);
+                (unsigned long long)pc.launches, pc.ms_kernel);
+    return 0;
 }
 
 }  // namespace mimeo

@@ -69,14 +69,20 @@ inline uint64_t chunks_of(const uint64_t *first, const mimeo_path_block *blocks,
 // The call as slices [a0, a1) of whole alignments: at most max_records records and max_blocks blocks each, so that the
 // upload of a slice is bounded whatever the job's size.  An alignment with more blocks than max_blocks is a slice of its own
 // (12 bytes per block: 2^24 blocks are 192 MiB, and no alignment comes near).  `first` has passed validate().
-inline std::vector<std::pair<uint64_t, uint64_t>> plan_slices(const uint64_t *first, uint64_t n, uint64_t max_records, uint64_t max_blocks) {
+// row_first (optional; K11, path_text_host.h): alignment i also makes row_first[i + 1] - row_first[i] output columns, and a
+// slice holds at most max_columns of them; an alignment of more is a slice of its own.
+inline std::vector<std::pair<uint64_t, uint64_t>> plan_slices(const uint64_t *first, uint64_t n, uint64_t max_records, uint64_t max_blocks,
+                                                              const uint64_t *row_first = nullptr, uint64_t max_columns = 0) {
     std::vector<std::pair<uint64_t, uint64_t>> s;
     if (max_records < 1) max_records = 1;
     if (max_blocks < 1) max_blocks = 1;
+    if (max_columns < 1) max_columns = 1;
     uint64_t a0 = 0;
     while (a0 < n) {
         uint64_t a1 = a0 + 1;
-        while (a1 < n && a1 - a0 < max_records && first[a1 + 1] - first[a0] <= max_blocks) a1++;
+        while (a1 < n && a1 - a0 < max_records && first[a1 + 1] - first[a0] <= max_blocks &&
+               (!row_first || row_first[a1 + 1] - row_first[a0] <= max_columns))
+            a1++;
         s.emplace_back(a0, a1);
         a0 = a1;
     }

@@ -59,18 +59,7 @@ inline void block_columns(const uint64_t *first, const mimeo_path_block *blocks,
 // cap is a slice of its own.
 inline std::vector<std::pair<uint64_t, uint64_t>> plan_slices(const uint64_t *row_first, const uint64_t *first, uint64_t n, uint64_t max_records,
                                                               uint64_t max_blocks, uint64_t max_columns) {
-    std::vector<std::pair<uint64_t, uint64_t>> s;
-    if (max_records < 1) max_records = 1;
-    if (max_blocks < 1) max_blocks = 1;
-    if (max_columns < 1) max_columns = 1;
-    uint64_t a0 = 0;
-    while (a0 < n) {
-        uint64_t a1 = a0 + 1;
-        while (a1 < n && a1 - a0 < max_records && first[a1 + 1] - first[a0] <= max_blocks && row_first[a1 + 1] - row_first[a0] <= max_columns) a1++;
-        s.emplace_back(a0, a1);
-        a0 = a1;
-    }
-    return s;
+    return path_stats_host::plan_slices(first, n, max_records, max_blocks, row_first, max_columns);
 }
 
 // One job = one wavefront of the kernel: the columns [c0, c1) of the row of alignment `aln` (index inside the slice).  An

@@ -180,17 +180,33 @@ def align_units(A, B, units, params=None, paths=False):
     return _ffi.take(ptr, n, _ffi.ALIGNMENT)
 
 
+def _paths(records, first, blocks):
+    """records / first / blocks of a path call as contiguous arrays of the ABI's types"""
+    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
+    first = np.ascontiguousarray(first, dtype=np.uint64)
+    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
+    if first.size != recs.size + 1:
+        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
+    return recs, first, blk
+
+
+def _window_items(items):
+    """_ffi.WINDOW_ITEM rows, or an (n, 4) array of (aln, group, w0, w1), as contiguous _ffi.WINDOW_ITEM rows"""
+    it = np.asarray(items)
+    if it.dtype != _ffi.WINDOW_ITEM:
+        a = np.asarray(it, dtype=np.uint32).reshape(-1, 4)
+        it = np.zeros(a.shape[0], dtype=_ffi.WINDOW_ITEM)
+        it['aln'], it['group'], it['w0'], it['w1'] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    return np.ascontiguousarray(it)
+
+
 def path_stats(A, B, records, first, blocks):
     """Column statistics of alignment paths (mimeo_path_stats, kernel K9): one _ffi.COLUMN_STATS row per record — matches,
     transitions, transversions and ambiguous columns of its blocks blocks[first[i]:first[i + 1]], insertion / deletion runs and
     bases between them.  records / first / blocks as align_pairs(..., paths=True) returns them (or any selection of them:
     formats.select_paths); B = None: the queries are scaffolds of A.  A path that breaks the contract of mimeo_path_block is a
     RuntimeError naming the record, raised before anything runs on the device."""
-    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
-    first = np.ascontiguousarray(first, dtype=np.uint64)
-    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
-    if first.size != recs.size + 1:
-        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
+    recs, first, blk = _paths(records, first, blocks)
     out = np.zeros(recs.size, dtype=_ffi.COLUMN_STATS)
     if recs.size:
         _ffi.check(_ffi.load().mimeo_path_stats(A._h, B._h if B is not None else None, recs.ctypes.data, recs.size, first.ctypes.data,
@@ -205,17 +221,8 @@ def window_stats(A, B, records, first, blocks, items, ngroups):
     [w0, w1) of its target scaffold's plus strand, and the gaps that start there (include/mimeo_hip.h has the rules), are added
     to the group.  Items come in any order; a group without items is zero.  A bad path or a bad item is a RuntimeError naming
     it, raised before anything runs on the device."""
-    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
-    first = np.ascontiguousarray(first, dtype=np.uint64)
-    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
-    if first.size != recs.size + 1:
-        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
-    it = np.asarray(items)
-    if it.dtype != _ffi.WINDOW_ITEM:
-        a = np.asarray(it, dtype=np.uint32).reshape(-1, 4)
-        it = np.zeros(a.shape[0], dtype=_ffi.WINDOW_ITEM)
-        it['aln'], it['group'], it['w0'], it['w1'] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
-    it = np.ascontiguousarray(it)
+    recs, first, blk = _paths(records, first, blocks)
+    it = _window_items(items)
     out = np.zeros(int(ngroups), dtype=_ffi.WINDOW_STATS)
     _ffi.check(_ffi.load().mimeo_path_window_stats(A._h, B._h if B is not None else None, recs.ctypes.data if recs.size else None, recs.size,
                                                    first.ctypes.data, blk.ctypes.data if blk.size else None, blk.size,
@@ -234,11 +241,7 @@ def link_regions(A, records, first, blocks, regions, chrom_of_tid, items, min_co
     min_cover_pct per cent of its region is projected through the record's path onto the query scaffold, and every other
     region of which the projection covers min_cover_pct per cent joins the family (include/mimeo_hip.h has the rule).  A bad
     path, region or item is a RuntimeError naming it, raised before anything runs on the device."""
-    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
-    first = np.ascontiguousarray(first, dtype=np.uint64)
-    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
-    if first.size != recs.size + 1:
-        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
+    recs, first, blk = _paths(records, first, blocks)
     lib = _ffi.load()
     if not hasattr(lib, 'mimeo_link_regions'):
         raise RuntimeError('libmimeo_hip.so has no mimeo_link_regions: rebuild the library')
@@ -248,12 +251,7 @@ def link_regions(A, records, first, blocks, regions, chrom_of_tid, items, min_co
         reg = np.zeros(a.shape[0], dtype=_ffi.INTERVAL)
         reg['chrom'], reg['start'], reg['end'] = a[:, 0], a[:, 1], a[:, 2]
     reg = np.ascontiguousarray(reg)
-    it = np.asarray(items)
-    if it.dtype != _ffi.WINDOW_ITEM:
-        a = np.asarray(it, dtype=np.uint32).reshape(-1, 4)
-        it = np.zeros(a.shape[0], dtype=_ffi.WINDOW_ITEM)
-        it['aln'], it['group'], it['w0'], it['w1'] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
-    it = np.ascontiguousarray(it)
+    it = _window_items(items)
     cot = None
     if chrom_of_tid is not None:
         cot = np.ascontiguousarray(chrom_of_tid, dtype=np.uint32)
@@ -275,11 +273,7 @@ def path_text(A, B, records, first, blocks):
     strand's, '-' where the other sequence jumps (insertions before deletions), A C G T and N for everything else — the device
     keeps neither case nor IUPAC codes (include/mimeo_hip.h has the rules).  records / first / blocks and the errors as for
     path_stats.  The arrays hold the whole call: a caller bounds them by what it asks for at once (workflow.text_runs)."""
-    recs = np.ascontiguousarray(records, dtype=_ffi.ALIGNMENT)
-    first = np.ascontiguousarray(first, dtype=np.uint64)
-    blk = np.ascontiguousarray(blocks, dtype=_ffi.PATH_BLOCK)
-    if first.size != recs.size + 1:
-        raise ValueError('first has %d entries for %d records (one more is needed)' % (first.size, recs.size))
+    recs, first, blk = _paths(records, first, blocks)
     lib = _ffi.load()
     if not hasattr(lib, 'mimeo_path_text'):
         raise RuntimeError('libmimeo_hip.so has no mimeo_path_text: rebuild the library')

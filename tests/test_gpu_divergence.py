@@ -194,9 +194,13 @@ def test_made_up_paths_equal_the_restatement(eng, made_up, monkeypatch):
     rev = np.arange(recs.size)[::-1]
     f2, b2 = formats.select_paths(first, blocks, rev)
     same(eng.path_stats(A, None, recs[rev], f2, b2), exp[rev], 'reversed')
-    # every alignment a slice of its own; alignments cut into jobs of one and of three chunks; never cut
+    # every alignment a slice of its own; alignments cut into jobs of one and of three chunks; never cut; one job per launch (a
+    # workgroup with three idle wavefronts) and three (a partial last workgroup); the jobs of a cut alignment in different
+    # launches; a launch cap that is no number or zero is the default
     for env in ({'MIMEO_PATH_STATS_SLICE_BLOCKS': '1'}, {'MIMEO_PATH_STATS_SPLIT_CHUNKS': '1'}, {'MIMEO_PATH_STATS_SPLIT_CHUNKS': '3'},
-                {'MIMEO_PATH_STATS_SPLIT_CHUNKS': '0'}, {'MIMEO_PATH_STATS_SLICE_BLOCKS': '70', 'MIMEO_PATH_STATS_SPLIT_CHUNKS': '2'}):
+                {'MIMEO_PATH_STATS_SPLIT_CHUNKS': '0'}, {'MIMEO_PATH_STATS_SLICE_BLOCKS': '70', 'MIMEO_PATH_STATS_SPLIT_CHUNKS': '2'},
+                {'MIMEO_PATH_LAUNCH_JOBS': '1'}, {'MIMEO_PATH_LAUNCH_JOBS': '3'}, {'MIMEO_PATH_STATS_SPLIT_CHUNKS': '1', 'MIMEO_PATH_LAUNCH_JOBS': '3'},
+                {'MIMEO_PATH_LAUNCH_JOBS': '0'}, {'MIMEO_PATH_LAUNCH_JOBS': 'abc'}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         same(eng.path_stats(A, None, recs, first, blocks), exp, env)   # the whole list, also with one launch per alignment

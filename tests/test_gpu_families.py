@@ -2,7 +2,9 @@
 restatement of "family linking v1" (include/mimeo_hip.h), written here from the rule alone: per alignment a map from every
 target base of [tstart, tend) to its query coordinate (-1 under a deletion), the projection of a window as the min and max of
 the map over it, a dict as the union-find, the family as the min of the component.  Equality is exact, for family and links."""
+import json
 import os
+import re
 import socket
 import subprocess
 import sys
@@ -369,6 +371,8 @@ def test_union_find_chain_star_and_pairs(eng, uf):
 
 
 CHILD = '''
+import json
+import os
 import sys
 import numpy as np
 from mimeo_amd import engine
@@ -376,16 +380,22 @@ engine.init(0)
 z = np.load(sys.argv[1])
 G = engine.Genome(['u0', 'u1', 'u2'], [np.full(int(n), ord('A'), dtype=np.uint8) for n in z['L']])
 out = {}
-for k in range(int(z['ncases'])):
-    fam, lnk = engine.link_regions(G, z['recs%d' % k], z['first%d' % k], z['blocks%d' % k], z['regions%d' % k], None, z['items%d' % k], int(z['pct%d' % k]))
-    out['fam%d' % k], out['lnk%d' % k] = fam, lnk
+for e, env in enumerate(json.loads(sys.argv[3])):   # the switches are read by every call
+    os.environ.update(env)
+    for k in range(int(z['ncases'])):
+        fam, lnk = engine.link_regions(G, z['recs%d' % k], z['first%d' % k], z['blocks%d' % k], z['regions%d' % k], None, z['items%d' % k], int(z['pct%d' % k]))
+        out['fam%d_%d' % (e, k)], out['lnk%d_%d' % (e, k)] = fam, lnk
+    for name in env:
+        del os.environ[name]
 np.savez(sys.argv[2], **out)
 '''
 
 
 def test_every_alignment_a_slice_of_its_own(eng, uf, tmp_path):
     """MIMEO_LINK_SLICE_BLOCKS=1 in a child process: the same arrays — the union-find lives across the slices.  Two cases: the
-    chain, star and pairs with every item once (13 000 slices of one block), and a few paths of many blocks."""
+    chain, star and pairs with every item once (13 000 slices of one block), and a few paths of many blocks.  Then the same two
+    cases under MIMEO_PATH_LAUNCH_JOBS: one job and three jobs per launch give the same arrays — the union-find lives across
+    the launches — and the statistics line counts the launches; zero and a word mean the default."""
     G, _, _, _, _, _, _ = uf
     recs, first, blocks, regions, items = uf_case(1)
     rng = np.random.default_rng(74)
@@ -412,17 +422,36 @@ def test_every_alignment_a_slice_of_its_own(eng, uf, tmp_path):
             z['%s%d' % (name, k)] = np.asarray(v)
     np.savez(tmp_path / 'in.npz', **z)
     (tmp_path / 'child.py').write_text(CHILD)
-    env = dict(os.environ, MIMEO_LINK_SLICE_BLOCKS='1', MIMEO_LINK_STATS='1', PYTHONPATH=os.pathsep.join(p for p in (ROOT, os.environ.get('PYTHONPATH')) if p))
-    r = subprocess.run([sys.executable, str(tmp_path / 'child.py'), str(tmp_path / 'in.npz'), str(tmp_path / 'out.npz')], cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=300)
+    envs = [{'MIMEO_LINK_SLICE_BLOCKS': '1'}, {}, {'MIMEO_PATH_LAUNCH_JOBS': '1'}, {'MIMEO_PATH_LAUNCH_JOBS': '3'}, {'MIMEO_PATH_LAUNCH_JOBS': '0'},
+            {'MIMEO_PATH_LAUNCH_JOBS': 'abc'}]
+    env = dict(os.environ, MIMEO_LINK_STATS='1', PYTHONPATH=os.pathsep.join(p for p in (ROOT, os.environ.get('PYTHONPATH')) if p))
+    for e in envs:
+        for name in e:
+            env.pop(name, None)
+    r = subprocess.run([sys.executable, str(tmp_path / 'child.py'), str(tmp_path / 'in.npz'), str(tmp_path / 'out.npz'), json.dumps(envs)], cwd=ROOT,
+                       env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     got = np.load(tmp_path / 'out.npz')
-    for k, (fam, lnk) in enumerate(here):
-        assert got['fam%d' % k].tobytes() == fam.tobytes() and got['lnk%d' % k].tobytes() == lnk.tobytes(), k
+    for e in range(len(envs)):
+        for k, (fam, lnk) in enumerate(here):
+            assert got['fam%d_%d' % (e, k)].tobytes() == fam.tobytes() and got['lnk%d_%d' % (e, k)].tobytes() == lnk.tobytes(), (envs[e], k)
     # the statistics line says what was done: every alignment that an item asks for a slice of its own
     lines = [l for l in r.stderr.splitlines() if l.startswith('[k12]')]
-    assert len(lines) == 2 and '%d items' % items.shape[0] in lines[0] and 'slices %d of %d' % (recs.size, recs.size) in lines[0], r.stderr
+    assert len(lines) == 2 * len(envs), r.stderr
+    assert '%d items' % items.shape[0] in lines[0] and 'slices %d of %d' % (recs.size, recs.size) in lines[0], r.stderr
     assert 'slices 12 of 12' in lines[1] and 'kernels' in lines[1]
+    # ... and how many launches it took: k12_init, k12_flatten and the launches of the jobs.  A job is an item that passes
+    # rule A (every path here has blocks): all 48 of the second case
+    jobs2 = sum(1 for a, k, w0, w1 in items2.tolist() if 100 * (w1 - w0) >= 30 * (regions2[k][2] - regions2[k][1]))
+    assert jobs2 == 48
+    said = [tuple(int(x) for x in re.search(r'(\d+) jobs, .* launches (\d+),', l).groups()) for l in lines]
+    assert all(j == jobs2 for j, _ in said[1::2]), r.stderr
+    launches = {json.dumps(e): (said[2 * i][1], said[2 * i + 1][1]) for i, e in enumerate(envs)}
+    assert launches['{}'][1] == 1 + 2                                               # one slice, one launch
+    assert launches[json.dumps({'MIMEO_LINK_SLICE_BLOCKS': '1'})][1] == 12 + 2     # a launch per slice
+    assert launches[json.dumps({'MIMEO_PATH_LAUNCH_JOBS': '1'})] == (said[0][0] + 2, jobs2 + 2)
+    assert launches[json.dumps({'MIMEO_PATH_LAUNCH_JOBS': '3'})] == ((said[0][0] + 2) // 3 + 2, (jobs2 + 2) // 3 + 2)
+    assert launches[json.dumps({'MIMEO_PATH_LAUNCH_JOBS': '0'})] == launches['{}'] == launches[json.dumps({'MIMEO_PATH_LAUNCH_JOBS': 'abc'})]
 
 
 # ---- edge inputs -----------------------------------------------------------------------------------------------------------

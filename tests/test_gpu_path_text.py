@@ -259,10 +259,14 @@ def test_made_up_paths_equal_the_restatement(eng, made_up, monkeypatch):
     rev = np.arange(recs.size)[::-1]
     f2, b2 = formats.select_paths(first, blocks, rev)
     same(eng.path_text(A, None, recs[rev], f2, b2), select_rows(exp, rev.tolist()), 'reversed')
-    # every alignment a slice of its own, small slices; rows cut into jobs of 16 and of 48 columns, never cut; both at once
+    # every alignment a slice of its own, small slices; rows cut into jobs of 16 and of 48 columns, never cut; both at once; one
+    # job per launch (a workgroup with three idle wavefronts) and three (a partial last workgroup); the jobs of a cut row in
+    # different launches; a launch cap that is no number or zero is the default
     for env in ({'MIMEO_PATH_TEXT_SLICE_COLUMNS': '1'}, {'MIMEO_PATH_TEXT_SLICE_COLUMNS': '100'}, {'MIMEO_PATH_TEXT_SLICE_COLUMNS': '4096'},
                 {'MIMEO_PATH_TEXT_SPLIT_COLUMNS': '16'}, {'MIMEO_PATH_TEXT_SPLIT_COLUMNS': '48'}, {'MIMEO_PATH_TEXT_SPLIT_COLUMNS': '0'},
-                {'MIMEO_PATH_TEXT_SLICE_COLUMNS': '700', 'MIMEO_PATH_TEXT_SPLIT_COLUMNS': '32'}):
+                {'MIMEO_PATH_TEXT_SLICE_COLUMNS': '700', 'MIMEO_PATH_TEXT_SPLIT_COLUMNS': '32'},
+                {'MIMEO_PATH_LAUNCH_JOBS': '1'}, {'MIMEO_PATH_LAUNCH_JOBS': '3'}, {'MIMEO_PATH_TEXT_SPLIT_COLUMNS': '16', 'MIMEO_PATH_LAUNCH_JOBS': '3'},
+                {'MIMEO_PATH_LAUNCH_JOBS': '0'}, {'MIMEO_PATH_LAUNCH_JOBS': 'abc'}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         same(eng.path_text(A, None, recs, first, blocks), exp, env)

@@ -379,7 +379,11 @@ def test_layout_independence(eng, made, monkeypatch):
     same(ref, exp, 'default')
     for env in ({'MIMEO_WINDOW_STATS_SPLIT_BASES': '64'}, {'MIMEO_WINDOW_STATS_SPLIT_BASES': '1000'}, {'MIMEO_WINDOW_STATS_SPLIT_BASES': '0'},
                 {'MIMEO_WINDOW_STATS_SLICE_BLOCKS': '1'}, {'MIMEO_WINDOW_STATS_SLICE_BLOCKS': '70', 'MIMEO_WINDOW_STATS_SPLIT_BASES': '100'},
-                {'MIMEO_WINDOW_STATS_STATS': '1'}):
+                {'MIMEO_WINDOW_STATS_STATS': '1'},
+                # one job per launch (a workgroup with three idle wavefronts) and three (a partial last workgroup); the pieces of a
+                # cut window in different launches; a launch cap that is no number or zero is the default
+                {'MIMEO_PATH_LAUNCH_JOBS': '1'}, {'MIMEO_PATH_LAUNCH_JOBS': '3'}, {'MIMEO_WINDOW_STATS_SPLIT_BASES': '64', 'MIMEO_PATH_LAUNCH_JOBS': '3'},
+                {'MIMEO_PATH_LAUNCH_JOBS': '0'}, {'MIMEO_PATH_LAUNCH_JOBS': 'abc'}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         assert run(eng, c, items, 41).tobytes() == ref.tobytes(), env
