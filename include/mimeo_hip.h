@@ -501,6 +501,62 @@ int mimeo_link_regions(const mimeo_genome *T, const mimeo_alignment *aln, uint64
                        uint32_t min_cover_pct, uint32_t *family /* caller's, nreg entries */, uint64_t *links /* caller's, nreg entries */);
 
 /*
+ * Column pileup of alignment paths and a base called from every column (kernel K13): the producer of a repeat library.  Where
+ * mimeo_path_window_stats collapses the columns of every alignment that piles up on a region to eight sums, this keeps the same
+ * pile PER COLUMN of the target, and calls a base from each: the consensus of the copies that align to a region, in the
+ * region's own coordinates.  Replaces nothing in the reference, which keeps no alignment; the sequences are read from the
+ * device-resident genomes, and no base text crosses the ABI on the way in.
+ *
+ * "Pileup v1".  T, Q, aln, n, path_first, blocks and nblocks are those of mimeo_path_stats.  Window g is [start, end) on the plus
+ * strand of target scaffold `tid`; column x of window g is entry col_first[g] + (x - start) of `cols` and of `call`, with
+ * col_first the prefix sum of end - start over the windows and ncols its total, in 64 bits.  Windows may overlap or repeat: each
+ * has columns of its own.  An item (aln, group, w0, w1) adds record `aln`, clipped to [w0, w1), to window `group`.
+ *
+ * Counts, per item and target base x in [w0, w1), with b_k, p_k, dt_k and dq_k as for mimeo_path_window_stats:
+ *   a c g t n   x lies under block b_k: with y the base of the aligned query strand at b_k.q + (x - b_k.t), the counter of y
+ *               grows by one where y is one of ACGT, and n where it is not (the N plane decides first).  The target's own base
+ *               plays no part in the counts;
+ *   del         x lies in a gap [p_k, b_k.t): del grows by one;
+ *   nothing     x lies outside [tstart, tend), or the record has no block;
+ *   ins_runs, ins_bases   for dq_k > 0 and w0 <= p_k < w1, column p_k gets ins_runs += 1 and ins_bases += dq_k: the insertion
+ *               sits in front of target base p_k and is never split — the rule of mimeo_path_window_stats.
+ * What follows, and what a caller may rely on:
+ *   - the counts are additive over any partition of an item's window;
+ *   - summed over a window's columns, a + c + g + t + n is matches + transitions + transversions + ambiguous of
+ *     mimeo_path_window_stats for the same items, del its del_bases, ins_runs and ins_bases its own;
+ *   - the counts are exact integers of 32 bits (a call in which more than 2^32 - 1 items name one window is refused) and depend
+ *     on nothing but the sequences, the blocks and the items.
+ *
+ * Call, per column, with x0 the target's own base (its letter A, C, G or T, or N for anything else):
+ *   votes      v[b] = count[b] + (x0 == b ? 1 : 0) for b in A, C, G, T, and vd = del: the region's own copy votes once;
+ *   winner     the largest vote.  Among equal votes x0 wins if it is one of them, otherwise the order is A, C, G, T; a deletion
+ *              wins only when it is strictly larger than every base;
+ *   byte       all five votes zero: 'N'; a winning deletion: '-'; otherwise the upper-case letter of the winner.
+ * So `call` always has ncols bytes, and a column that nobody covers calls the target's own letter.  A limit of v1: nothing is
+ * inserted into the call; insertions are reported through ins_runs / ins_bases, and a consumer decides.
+ *
+ * Everything is checked before the device sees it; a violation is MIMEO_ERR_ARG with a message that starts with
+ * "mimeo_path_pileup:" and names the item, the window, or the record and the block: everything mimeo_path_stats checks; per
+ * window tid inside T, start <= end and end <= the scaffold's length; per item aln < n, group < nwin, the record's tid equal to
+ * the window's, and start <= w0 <= w1 <= end.  nwin == 0 returns MIMEO_OK at once; nitems == 0 leaves zero counts and the target's
+ * own letters.  cols and call may each be NULL.  Records and blocks go to the device in the same bounded slices as for
+ * mimeo_path_stats, and only the slices that an item asks for; the columns are worked off in batches of a bounded number, so a
+ * call of any ncols runs in the memory that is free next to the genomes.
+ *
+ * A new symbol beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs it checks for the symbol.
+ */
+typedef struct mimeo_pileup_window {
+    uint32_t tid, start, end;
+} mimeo_pileup_window;                                         /* 12 bytes */
+typedef struct mimeo_pileup_column {
+    uint32_t a, c, g, t, n, del, ins_runs, ins_bases;
+} mimeo_pileup_column;                                         /* 32 bytes */
+int mimeo_path_pileup(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, const mimeo_alignment *aln, uint64_t n,
+                      const uint64_t *path_first, const mimeo_path_block *blocks, uint64_t nblocks,
+                      const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items, uint64_t nitems,
+                      mimeo_pileup_column *cols /* caller's, ncols entries, or NULL */, uint8_t *call /* caller's, ncols bytes, or NULL */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  A left-out pair is a scaffold pair: EVERY entry of the

@@ -93,6 +93,18 @@ def add_families(parser):
                              'element families; identity is governed by --minIdt.')
 
 
+def add_consensus(parser):
+    """--consensus of `mimeo self` (`mimeo x` has its query in another genome; `mimeo map` and `mimeo filter` read a library)"""
+    parser.add_argument('--consensus', type=str, default=None, metavar='FILE',
+                        help='Also write a repeat library to FILE: one FASTA record per repeat family (the families of --families, which '
+                             'need not be given; --familyCover applies), named F1, F2, ... (with --strictSelf the same-scaffold block '
+                             'follows as F1_intra, ...). The sequence is the consensus of the alignments that pile up on the family\'s '
+                             'representative feature, called column by column on the GPU; the header names the feature, its position, '
+                             'the members of the family, the mean depth of the pile and the columns at which most copies carry an '
+                             'insertion (which the consensus leaves out). Ready for mimeo filter and mimeo map. Off by default: without '
+                             'it no path is computed. Nothing is written with --recycle when the alignment file exists.')
+
+
 def check_families(parser, args):
     """--familyCover of `mimeo self` (parser.error exits with status 2, before the engine starts)"""
     if not 1 <= args.familyCover <= 100:

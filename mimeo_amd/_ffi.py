@@ -19,7 +19,7 @@ SYMBOLS = [
     'mimeo_coverage_collapse', 'mimeo_tandem_masked', 'mimeo_genome_load_fasta', 'mimeo_genome_name',
     'mimeo_genome_keep_indexes', 'mimeo_genome_drop_indexes', 'mimeo_genome_build_indexes', 'mimeo_coverage_bedgraph',
     'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths', 'mimeo_path_stats',
-    'mimeo_path_window_stats', 'mimeo_path_text', 'mimeo_link_regions',
+    'mimeo_path_window_stats', 'mimeo_path_text', 'mimeo_link_regions', 'mimeo_path_pileup',
 ]
 
 
@@ -71,6 +71,8 @@ COLUMN_STATS = np.dtype([(n, '<u4') for n in ('matches', 'transitions', 'transve
                                                'del_bases')])   # mimeo_column_stats, 32 bytes
 WINDOW_ITEM = np.dtype([(n, '<u4') for n in ('aln', 'group', 'w0', 'w1')])   # mimeo_window_item, 16 bytes
 WINDOW_STATS = np.dtype([(n, '<u8') for n in COLUMN_STATS.names])   # mimeo_window_stats, 64 bytes: the fields of mimeo_column_stats in 64 bits
+PILEUP_WINDOW = np.dtype([(n, '<u4') for n in ('tid', 'start', 'end')])   # mimeo_pileup_window, 12 bytes
+PILEUP_COLUMN = np.dtype([(n, '<u4') for n in ('a', 'c', 'g', 't', 'n', 'del', 'ins_runs', 'ins_bases')])   # mimeo_pileup_column, 32 bytes
 DEPTH_RUN = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4'), ('depth', '<u4')])
 
 _lib = None
@@ -124,6 +126,8 @@ def load():
         lib.mimeo_path_text.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     if hasattr(lib, 'mimeo_link_regions'):
         lib.mimeo_link_regions.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp]
+    if hasattr(lib, 'mimeo_path_pileup'):
+        lib.mimeo_path_pileup.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, vp]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

@@ -427,6 +427,16 @@ int mimeo_link_regions(const mimeo_genome *T, const mimeo_alignment *aln, uint64
     return link_regions_device(T, aln, n, path_first, blocks, nblocks, regions, nreg, chrom_of_scaf, items, nitems, min_cover_pct, family, links);
 }
 
+int mimeo_path_pileup(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first,
+                      const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
+                      uint64_t nitems, mimeo_pileup_column *cols, uint8_t *call) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!nwin) return MIMEO_OK;
+    if (!T || !windows || (nitems && !items) || (n && (!aln || !path_first)) || (nblocks && !blocks)) { set_error("mimeo_path_pileup: null argument"); return MIMEO_ERR_ARG; }
+    return path_pileup_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, windows, nwin, items, nitems, cols, call);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

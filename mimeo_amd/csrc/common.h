@@ -370,5 +370,10 @@ int path_text_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_a
 int link_regions_device(const mimeo_genome *T, const mimeo_alignment *aln, uint64_t n, const uint64_t *first, const mimeo_path_block *blocks,
                         uint64_t nblocks, const mimeo_interval *regions, uint64_t nreg, const uint32_t *chrom_of_scaf, const mimeo_window_item *items,
                         uint64_t nitems, uint32_t min_cover_pct, uint32_t *family, uint64_t *links);
+// K13: the pile of the alignments per target column and a base called from each (k13_pileup.hip); host in, host out.  Q is never
+// null here, and nwin > 0; cols and call may each be null.
+int path_pileup_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
+                       const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
+                       uint64_t nitems, mimeo_pileup_column *cols, uint8_t *call);
 
 }  // namespace mimeo

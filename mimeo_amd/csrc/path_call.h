@@ -1,6 +1,7 @@
 // path_call.h — what the kernels that consume alignment paths share (K9 k9_path_stats.hip, K10 k10_window_stats.hip,
 // K11 k11_path_text.hip, K12 k12_link_regions.hip): on the host one driver of a call (PathCall), on the device the skeleton
-// of a kernel that gives one wavefront to a job over the blocks of one alignment.  The next consumer of paths starts here.
+// of a kernel that gives one wavefront to a job over the blocks of one alignment.  The next consumer of paths starts here: K13
+// (k13_pileup.hip) takes the driver and the block search, and gives a workgroup to a tile of target columns.
 #pragma once
 #include <algorithm>
 #include <cstdlib>

@@ -267,6 +267,38 @@ def link_regions(A, records, first, blocks, regions, chrom_of_tid, items, min_co
     return family, links
 
 
+def pileup(A, B, records, first, blocks, windows, items, counts=True, call=True):
+    """Column pileup of alignment paths and a base called from every column (mimeo_path_pileup, kernel K13): (cols, call) —
+    cols one _ffi.PILEUP_COLUMN row per column of every window (what the aligned query strands put on that target base: a, c, g,
+    t, n, del, and the insertions in front of it), call one byte per column (the letter with the most votes, the target's own
+    base voting once; '-' where deletions outnumber every base; include/mimeo_hip.h "pileup v1" has the rules).  The columns of
+    window g start at entry sum(end - start of the windows before it).  records / first / blocks as for path_stats; windows:
+    _ffi.PILEUP_WINDOW rows (or an (n, 3) array) of (tid, start, end) on the target's plus strand, overlapping or repeated as
+    they come; items: _ffi.WINDOW_ITEM rows (or an (n, 4) array) of (record number, window number, w0, w1) with [w0, w1) inside
+    the window.  counts=False / call=False: that array is not computed and None comes back in its place.  A bad path, window or
+    item is a RuntimeError naming it, raised before anything runs on the device."""
+    recs, first, blk = _paths(records, first, blocks)
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_path_pileup'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_path_pileup: rebuild the library')
+    win = np.asarray(windows)
+    if win.dtype != _ffi.PILEUP_WINDOW:
+        a = np.asarray(win, dtype=np.uint32).reshape(-1, 3)
+        win = np.zeros(a.shape[0], dtype=_ffi.PILEUP_WINDOW)
+        win['tid'], win['start'], win['end'] = a[:, 0], a[:, 1], a[:, 2]
+    win = np.ascontiguousarray(win)
+    it = _window_items(items)
+    # the arrays are sized by what the library will accept: a window with start > end is refused there, before anything is written
+    ncols = int(np.maximum(win['end'].astype(np.int64) - win['start'].astype(np.int64), 0).sum())
+    cols = np.zeros(ncols, dtype=_ffi.PILEUP_COLUMN) if counts else None
+    letters = np.zeros(ncols, dtype=np.uint8) if call else None
+    _ffi.check(lib.mimeo_path_pileup(A._h, B._h if B is not None else None, recs.ctypes.data if recs.size else None, recs.size, first.ctypes.data,
+                                     blk.ctypes.data if blk.size else None, blk.size, win.ctypes.data if win.size else None, win.size,
+                                     it.ctypes.data if it.size else None, it.size, cols.ctypes.data if counts and ncols else None,
+                                     letters.ctypes.data if call and ncols else None))
+    return cols, letters
+
+
 def path_text(A, B, records, first, blocks):
     """The text of alignment paths (mimeo_path_text, kernel K11): (row_first, trow, qrow) as numpy arrays (<u8, uint8, uint8).
     Row i is trow[row_first[i]:row_first[i + 1]] over the same range of qrow: the target's letters over the aligned query

@@ -456,6 +456,53 @@ def family_lines(regions, names_sorted, prefix, family, links, suffix='', header
     return lines
 
 
+def family_representatives(regions, family, links):
+    """The region that stands for each family in --consensus: the member with the most links (the copy that the most alignments
+    tie to the others), among those the longest, among those the first.  family / links: what engine.link_regions returned.
+    Returns one (region number, members) per family, in the order of family_lines' names F1, F2, ... (that of the families'
+    first members); a family of one is represented by its only member."""
+    order, best, members = [], {}, {}
+    for i, (r, f) in enumerate(zip(regions, (int(f) for f in family))):
+        key = (int(links[i]), int(r['end']) - int(r['start']))
+        if f not in best:
+            order.append(f)
+            best[f] = (key, i)
+        elif key > best[f][0]:   # strictly: an equal later member does not replace an earlier one
+            best[f] = (key, i)
+        members[f] = members.get(f, 0) + 1
+    return [(best[f][1], members[f]) for f in order]
+
+
+PILEUP_DEPTH_FIELDS = ('a', 'c', 'g', 't', 'n', 'del')
+CONSENSUS_WIDTH = 60
+
+
+def consensus_records(regions, names_sorted, prefix, reps, cols, call, suffix='', number=1):
+    """--consensus: one FASTA record per family, in the order of family_lines' names.  reps: family_representatives; cols / call:
+    what engine.pileup returned for the representatives' regions as windows, in the order of reps (window k starts at the summed
+    length of the windows before it).  The sequence is the call bytes of the representative's window with '-' removed (a column
+    where deletions outnumber every base is not part of the family), CONSENSUS_WIDTH letters per line.  The header is
+    >F3 rep=<ID> <seqid>:<start>-<end> members=<m> length=<len> mean_depth=<%.2f> ins_sites=<k>: ID, seqid, start and end those of
+    the representative's GFF3 row, length that of the sequence, mean_depth the mean of a + c + g + t + n + del over the window
+    (the alignment rows per base; the region's own copy is not counted), ins_sites the number of columns in front of which most
+    of the pile inserts something: 2 * ins_runs > a + c + g + t + n + del + 1 (the own copy, which inserts nothing, counted
+    in).  pileup v1 inserts nothing into the call; ins_sites says how often that matters.  number: that of the first family of
+    reps (a caller that works the families off in runs).  Returns the lines."""
+    lines, at = [], 0
+    for k, (i, members) in enumerate(reps, number):
+        r = regions[i]
+        n = int(r['end']) - int(r['start'])
+        c = cols[at:at + n]
+        depth = sum(c[f].astype(np.int64) for f in PILEUP_DEPTH_FIELDS) if n else np.zeros(0, dtype=np.int64)
+        seq = bytes(np.asarray(call[at:at + n], dtype=np.uint8).tobytes()).replace(b'-', b'').decode('ascii')
+        at += n
+        lines.append('>F%d%s rep=%s_%05d %s:%d-%d members=%d length=%d mean_depth=%.2f ins_sites=%d' % (
+            k, suffix, prefix, i + 1, names_sorted[int(r['chrom'])], int(r['start']), int(r['end']), members, len(seq),
+            float(depth.sum()) / n if n else 0.0, int((2 * c['ins_runs'].astype(np.int64) > depth + 1).sum()) if n else 0))
+        lines.extend(seq[j:j + CONSENSUS_WIDTH] for j in range(0, len(seq), CONSENSUS_WIDTH))
+    return lines
+
+
 def import_align(tab_rows, prefix=None, min_len=100, min_idt=95):
     """wrappers.py:33-117 import_Align: re-filter on int(end)-int(start) and float(pID); sort on
     the STRING columns tName, tStart, tEnd, tStrand (lexicographic, stable); UID = prefix_<rank>

@@ -14,6 +14,7 @@ def mainArgs(argv=None):
     parser.add_argument('--bedtools', type=str, default='bedtools', help='Accepted for compatibility; bedtools is not used.')
     _cli.add_region_stats(parser)
     _cli.add_families(parser)
+    _cli.add_consensus(parser)
     parser.add_argument('--minCov', type=int, default=3, help='Minimum depth of aligned segments to report repeat feature.')
     parser.add_argument('--intraCov', type=int, default=5,
                         help='Minimum depth of aligned segments from same scaffold to report feature. Used if "--strictSelf" mode is selected.')
@@ -37,7 +38,8 @@ def main(argv=None):
                           minCov=args.minCov, intraCov=args.intraCov, splitSelf=args.strictSelf, reuseTab=args.recycle,
                           label=args.label, prefix=args.prefix, dist=dist,
                           anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence,
-                          region_stats=args.regionStats, maf=args.maf, cs=args.cs, families=args.families, family_cover=args.familyCover)
+                          region_stats=args.regionStats, maf=args.maf, cs=args.cs, families=args.families, family_cover=args.familyCover,
+                          consensus=args.consensus)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

@@ -272,6 +272,14 @@ def family_block(A, kept_paths, select, regions, prefix, cover, suffix, header):
     """--families for one block of GFF3 rows: the rows `select` (a mask) of the kept rows' (records, first, blocks) joined with
     `regions` (formats.region_items, without the trivial self rows), one engine.link_regions call (kernel K12), the lines of
     formats.family_lines."""
+    _, names_sorted, _, family, links = linked_regions(A, kept_paths, select, regions, cover)
+    return formats.family_lines(regions, names_sorted, prefix, family, links, suffix=suffix, header=header)
+
+
+def linked_regions(A, kept_paths, select, regions, cover):
+    """What --families and --consensus share for one block of GFF3 rows: the rows `select` (a mask) of the kept rows' (records,
+    first, blocks) joined with `regions` (formats.region_items, without the trivial self rows) and one engine.link_regions call
+    (kernel K12).  Returns ((records, first, blocks) of the rows, the sorted names, the items, family, links)."""
     recs, first, blk = kept_paths
     rows = np.flatnonzero(select)
     f2, b2 = formats.select_paths(first, blk, rows)
@@ -280,13 +288,44 @@ def family_block(A, kept_paths, select, regions, prefix, cover, suffix, header):
     chrom_of_tid = [cid[n] for n in A.names]
     items, _ = formats.region_items(recs[rows], regions, chrom_of_tid, first=f2, blocks=b2, self_job=True)
     family, links = engine.link_regions(A, recs[rows], f2, b2, regions, chrom_of_tid, items, cover)
-    return formats.family_lines(regions, names_sorted, prefix, family, links, suffix=suffix, header=header)
+    return (recs[rows], f2, b2), names_sorted, items, family, links
+
+
+CONSENSUS_BUDGET = 1 << 22   # columns asked of engine.pileup at once: 128 MiB of counts on the host
+
+
+def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budget=CONSENSUS_BUDGET):
+    """--consensus for one block of GFF3 rows: the families exactly as family_block computes them, of every family the
+    representative region (formats.family_representatives) as a window, the items of those regions (formats.region_items,
+    without the trivial self rows) as the pile, engine.pileup (kernel K13) in runs of windows of at most `budget` columns (a
+    longer window goes alone), the lines of formats.consensus_records.  The lines do not depend on the budget."""
+    (recs, f2, b2), names_sorted, items, family, links = linked_regions(A, kept_paths, select, regions, cover)
+    reps = formats.family_representatives(regions, family, links)
+    tid_of = {n: i for i, n in enumerate(A.names)}
+    rep = np.array([i for i, _ in reps], dtype=np.int64)
+    windows = np.zeros(rep.size, dtype=engine._ffi.PILEUP_WINDOW)
+    if rep.size:
+        windows['tid'] = [tid_of[names_sorted[int(c)]] for c in regions['chrom'][rep]]
+        windows['start'], windows['end'] = regions['start'][rep], regions['end'][rep]
+    window_of = np.full(len(regions), -1, dtype=np.int64)
+    window_of[rep] = np.arange(rep.size)
+    its = items[window_of[items['group'].astype(np.int64)] >= 0] if items.size else items
+    its = its.copy()
+    its['group'] = window_of[its['group'].astype(np.int64)]
+    its = its[np.argsort(its['group'], kind='stable')]
+    lines = []
+    for g0, g1 in text_runs(windows['end'].astype(np.int64) - windows['start'], budget):
+        run = its[np.searchsorted(its['group'], g0, side='left'):np.searchsorted(its['group'], g1, side='left')].copy()
+        run['group'] -= g0
+        cols, call = engine.pileup(A, None, recs, f2, b2, windows[g0:g1], run)
+        lines += formats.consensus_records(regions, names_sorted, prefix, reps[g0:g1], cols, call, suffix=suffix, number=g0 + 1)
+    return lines
 
 
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
                  B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None, maf=None, cs=False,
-                 text_budget=TEXT_BUDGET, families=None, family_cover=80):
+                 text_budget=TEXT_BUDGET, families=None, family_cover=80, consensus=None, consensus_budget=CONSENSUS_BUDGET):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
@@ -303,12 +342,21 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     K12): two regions are of one family when an alignment row that covers family_cover per cent of the one projects, through
     its path, onto family_cover per cent of the other (include/mimeo_hip.h "family linking v1").  Like region_stats it asks the
     alignment call for the paths, runs on rank 0 and adds no collective; with splitSelf the intra block is linked on its own
-    and its families are named F1_intra ...; nothing is written when the TAB is recycled or a pair is listed twice."""
+    and its families are named F1_intra ...; nothing is written when the TAB is recycled or a pair is listed twice.  consensus
+    (`mimeo self` only: ValueError with B): also write, to this file, one FASTA record per repeat family with the family's
+    consensus sequence (--consensus; consensus_block, formats.consensus_records, kernel K13): the families are computed exactly
+    as for `families` (family_cover applies; `families` itself is not needed), every family's representative region is a window,
+    the alignment rows over it are piled up per column in runs of at most consensus_budget columns, and a base is called from
+    each column (include/mimeo_hip.h "pileup v1") — a repeat library for `mimeo filter` and `mimeo map`.  It asks the alignment
+    call for the paths, runs on rank 0 and adds no collective; with splitSelf the intra block follows with F*_intra names;
+    nothing is written when the TAB is recycled or a pair is listed twice."""
     dist = dist or Dist()
     cs = cs and paf is not None
     if families is not None and B is not None:
         raise ValueError('families needs a self job: the regions and the queries must lie in one genome')
-    if families is not None and not 1 <= int(family_cover) <= 100:
+    if consensus is not None and B is not None:
+        raise ValueError('consensus needs a self job: the regions and the queries must lie in one genome')
+    if (families is not None or consensus is not None) and not 1 <= int(family_cover) <= 100:
         raise ValueError('family_cover must be in 1..100, not %r' % (family_cover,))
     kept_paths = None
     outtab_intra = outtab + '_intra.tab'
@@ -316,9 +364,9 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
         blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist,
-                                               paths=paf is not None or region_stats is not None or maf is not None or families is not None,
+                                               paths=paf is not None or region_stats is not None or maf is not None or families is not None or consensus is not None,
                                                divergence=divergence and paf is not None, paf_rows=paf is not None)
-        if region_stats is not None or families is not None:
+        if region_stats is not None or families is not None or consensus is not None:
             kept_paths = more[1]
         if paf is not None and dist.rank == 0:
             write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None, cs=(A, B, more[1], blocks, text_budget) if cs else None)
@@ -382,6 +430,19 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
                 fl += family_block(A, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), int(family_cover), '_intra', False)
             with open(families, 'w') as f:
                 for line in fl:
+                    f.write(line + '\n')
+    if consensus is not None:
+        if kept_paths is None:
+            logging.warning('--consensus needs the alignments\' paths: none with a recycled alignment file or a pair listed twice; %s is not written',
+                            consensus)
+        else:
+            none = np.zeros(0, dtype=engine._ffi.INTERVAL)
+            cl = consensus_block(A, kept_paths, ~intra if splitSelf else np.ones(kept.shape[0], bool), reg_main[0] if reg_main else none, str(prefix),
+                                 int(family_cover), '', consensus_budget)
+            if splitSelf:   # the intra block's families follow, as in --families
+                cl += consensus_block(A, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), int(family_cover), '_intra', consensus_budget)
+            with open(consensus, 'w') as f:
+                for line in cl:
                     f.write(line + '\n')
     return lines
 
