@@ -15,10 +15,10 @@ constexpr int LONG_WINDOWS = 8;  // per-lane walks give up after 8*32 bases per 
 // beyond the frame, follower sort and resolution, entropy) run once per batch.  A record names its unit; the
 // kernels look the two strands up in the unit table.
 struct ExtCounters {
-    unsigned long long ncand, nfollow, nlong, nhsp, nmed, nbig, nwalked;  // nwalked: hits the pre-filter let through
+    unsigned long long ncand, nfollow, nlong, nhsp, nbig, nwalked;  // nwalked: hits the pre-filter let through
     // The two busy queues — followers and hits whose walk outlives the frame — are filled in eight shards (workgroup
     // number mod 8, i.e. per XCD: region r = [r * cap, ...)): a same-address atomic serialises at ~13 ns and a C4 unit
-    // makes ~10^4 flushes.  nfollow / nmed hold the totals once k4_compact has gathered the follower shards.
+    // makes ~10^4 flushes.  nfollow holds the total once k4_compact_followers has gathered the follower shards.
     unsigned long long nfollow8[8], nmed8[8];
     unsigned long long nbigcand;   // candidates longer than ENT_LONG columns: their entropy is counted by the whole grid
     unsigned long long long_next, seg_next;  // k4_extend_long / k4_resolve_segments: next long hit / large segment to hand out
@@ -39,6 +39,7 @@ struct Cand {
     uint32_t unit;
 };
 constexpr int32_t RAW_SATURATED = 0x7FFFFFFF;
+struct FollowRec { uint64_t key; uint32_t prev; };   // a follower: its key (below) and the nearest earlier seed end (or RUN_END)
 
 // Batch-wide output queues of the heavy kernels and of the walks behind them.  Every append is guarded by the queue's
 // capacity while the counter keeps counting, so the host sees an overflow as "counter > capacity" and repeats the
@@ -61,7 +62,8 @@ struct ExtQueues {
     unsigned long long *bigacc;     // ... matched A / C / G / T columns, raw score
     unsigned long long *unit_hits;  // seed hits per unit (statistics)
     unsigned long long *tile_hits;  // ... per unit and tile (K34 writes them, k34_sum_hits folds them into unit_hits)
-    uint64_t cand_cap, follow_cap, med_cap, long_cap, walk_cap;   // follow_cap, med_cap, walk_cap: per shard (shard r = base[r * cap ...])
+    uint64_t cand_cap, follow_cap, med_cap, long_cap;   // follow_cap, med_cap: per shard (k4_queue.h: ShardMap)
+    uint64_t walk_cap;        // not used: a unit's walk-queue shards have FusedUnit::walk_cap entries (the field stays because K34's argument block embeds this struct)
     uint32_t ebits, dbits;
 };
 // bit 31 of a walk-queue entry's x (POS_MASK leaves it free): K34's first pass ran the sharp filter on this pair at its flush and
@@ -501,41 +503,14 @@ __device__ __forceinline__ bool hit_needs_walk(const GStrandView &T, const GStra
 }
 
 // the exact walk of one hit from its frame: classifies it (to the generic kernel / follower / candidate)
-template <int VARIANT>
 __device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const GStrandView &T, const GStrandView &Q,
                                          const uint2 h, int xdrop, int hspthresh, int transitions, bool &q_med,
-                                         uint2 &r_st, bool &q_fol, bool &q_cd, uint64_t &r_fk, uint32_t &r_fp, Cand &r_cd) {
+                                         uint2 &r_st, bool &q_fol, bool &q_cd, FollowRec &r_f, Cand &r_cd) {
     const int32_t et = (int32_t)h.x + SEED_LEN, eq = (int32_t)h.y + SEED_LEN;
     const int32_t d = (int32_t)h.x - (int32_t)h.y;
     const uint32_t bt = h.x & 31u;
     Frame F;
-    if (VARIANT == 8) {  // loads only, with the address pattern of a two-plane (8 bytes per 32 bases) copy: timing experiment
-        const uint32_t bq = h.y & 31u;
-        const int32_t wt = (int32_t)(h.x >> 5) - 2, wq = (int32_t)(h.y >> 5) - 2 - (bq < bt ? 1 : 0);
-        const gptr<uint2> t2 = T.pw.as<uint2>(), q2 = Q.pw.as<uint2>();
-        uint32_t acc = 0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) { const uint2 v = t2[wt + k]; acc ^= v.x ^ v.y; }
-#pragma unroll
-        for (int k = 0; k < 7; k++) { const uint2 v = q2[wq + k]; acc ^= v.x ^ v.y; }
-        if (acc == 0x12345678u) q_med = true;
-        return;
-    }
-    if (VARIANT == 3) {  // compute only (timing experiment, wrong results)
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            F.dl[k] = h.x * (k + 1); F.dh[k] = h.y + k; F.cg[k] = h.y * (k + 3); F.nn[k] = 0; F.st[k] = ~0u; F.sq[k] = ~0u;
-        }
-    } else {
-        load_frame(T, Q, h, F);
-    }
-    if (VARIANT == 2) {  // loads only (timing experiment, wrong results)
-        uint32_t acc = 0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) acc ^= F.dl[k] ^ F.dh[k] ^ F.cg[k] ^ F.nn[k] ^ F.st[k] ^ F.sq[k];
-        if (acc == 0x12345678u) q_med = true;
-        return;
-    }
+    load_frame(T, Q, h, F);
     // ---- left walk: up to two windows from the frame (the seed starts at frame bit 64 + bt)
     WalkState L{0, 0, 0, 0, false, false, 0};
     const uint32_t maxl = (uint32_t)min(et, eq);
@@ -547,12 +522,12 @@ __device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const
         r_st = pack_resume(0u, L.run, L.best, L.bk, 0, 0u);
     } else if (L.found) {
         q_fol = true;
-        r_fk = ((uint64_t)(uint32_t)(d + (int32_t)Q.len) << 32) | (uint32_t)et;  // the batch key is composed when the record is flushed
-        r_fp = (uint32_t)et - L.found_step;
+        r_f.key = ((uint64_t)(uint32_t)(d + (int32_t)Q.len) << 32) | (uint32_t)et;  // the batch key is composed when the record is stored (FollowerSink<true>)
+        r_f.prev = (uint32_t)et - L.found_step;
         if (L.found_step == 1) {   // a member of a run of consecutive seed hits: only the run's ends leave records
             const bool two_back = seed_hit_at(T, Q, (int32_t)h.x - 2, d, transitions), ahead = seed_hit_at(T, Q, (int32_t)h.x + 1, d, transitions);
             if (two_back && ahead) q_fol = false;     // interior
-            else if (two_back) r_fp = RUN_END;        // the last one (and not the first)
+            else if (two_back) r_f.prev = RUN_END;        // the last one (and not the first)
         }
     } else {
         // ---- right walk: two windows from the frame (frame bit of the seed end = 64 + bt + 19)
@@ -575,112 +550,12 @@ __device__ __forceinline__ void walk_hit(const uint32_t *__restrict__ tab, const
     }
 }
 
-// ---- per-wavefront staging of the records the exact walks produce ---------------------------------------
-// One global atomic serves >= 64 records instead of one per wavefront iteration (same-address atomics serialise
-// at ~12-15 ns each).  s_med / s_fk / s_fp (and s_cd when STAGE_CAND) are QCAP-entry LDS arrays private to the
-// wavefront (CAP entries for the frequent kinds, generic-walk hits and followers); the fill levels are wave-uniform
-// registers of the caller.  A queue is flushed when the new records would not fit (a batch adds at most 64); `final`
-// flushes what is left.  Follower records are
-// staged as (diagonal + Q.len) << 32 | seed end and get their batch key (unit, bit widths) at the flush.
-// A generic-walk record is 16 bytes (hit and walk state, pack_resume): s_med has MCAP entries of its own, so that
-// the array costs what CAP 8-byte hits did.
-struct WaveFill { uint32_t n_med, n_fol, n_cd; };
-
-__device__ __forceinline__ uint64_t batch_key(const ExtQueues &q, uint32_t unit, uint64_t staged) {
-    return ((uint64_t)unit << (q.dbits + q.ebits)) | ((staged >> 32) << q.ebits) | (staged & 0xFFFFFFFFull);
-}
-
-template <bool STAGE_CAND, int CAP = QCAP, int MCAP = CAP>
-__device__ __forceinline__ void stage_records(const ExtQueues &q, uint32_t unit, uint4 *s_med, uint64_t *s_fk, uint32_t *s_fp,
-                                              Cand *s_cd, WaveFill &f, bool q_med, uint2 h, uint2 r_st, bool q_fol, uint64_t r_fk,
-                                              uint32_t r_fp, bool q_cd, Cand r_cd, bool final) {
-    static_assert(MCAP >= 64 && CAP >= 64, "a batch adds up to 64 records of a kind");
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    uint64_t m = __ballot(q_med);
-    if (m || (final && f.n_med)) {
-        const uint32_t add = (uint32_t)__popcll(m);
-        if (f.n_med + add > (uint32_t)MCAP || (final && !m)) {
-            __builtin_amdgcn_wave_barrier();  // LDS accesses of one wavefront execute in order
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(&q.ctr->nmed8[queue_shard()], (unsigned long long)f.n_med);
-            b = __shfl(b, 0);
-            for (uint32_t i = lane; i < f.n_med; i += 64)
-                if (b + i < q.med_cap) { const size_t at = (size_t)queue_shard() * q.med_cap + b + i; q.medq[at] = s_med[i]; q.medu[at] = unit; }
-            f.n_med = 0;
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (q_med) s_med[f.n_med + __popcll(m & lt_mask)] = make_uint4(h.x, h.y, r_st.x, r_st.y);
-        f.n_med += add;
-        if (final && f.n_med) {
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(&q.ctr->nmed8[queue_shard()], (unsigned long long)f.n_med);
-            b = __shfl(b, 0);
-            for (uint32_t i = lane; i < f.n_med; i += 64)
-                if (b + i < q.med_cap) { const size_t at = (size_t)queue_shard() * q.med_cap + b + i; q.medq[at] = s_med[i]; q.medu[at] = unit; }
-            f.n_med = 0;
-        }
-    }
-    m = __ballot(q_fol);
-    if (m || (final && f.n_fol)) {
-        const uint32_t add = (uint32_t)__popcll(m);
-        if (f.n_fol + add > (uint32_t)CAP || (final && !m)) {
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(&q.ctr->nfollow8[queue_shard()], (unsigned long long)f.n_fol);
-            b = __shfl(b, 0);
-            for (uint32_t i = lane; i < f.n_fol; i += 64)
-                if (b + i < q.follow_cap) { const size_t at = (size_t)queue_shard() * q.follow_cap + b + i; q.fkey[at] = batch_key(q, unit, s_fk[i]); q.fprev[at] = s_fp[i]; }
-            f.n_fol = 0;
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (q_fol) { const uint32_t i = f.n_fol + __popcll(m & lt_mask); s_fk[i] = r_fk; s_fp[i] = r_fp; }
-        f.n_fol += add;
-        if (final && f.n_fol) {
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(&q.ctr->nfollow8[queue_shard()], (unsigned long long)f.n_fol);
-            b = __shfl(b, 0);
-            for (uint32_t i = lane; i < f.n_fol; i += 64)
-                if (b + i < q.follow_cap) { const size_t at = (size_t)queue_shard() * q.follow_cap + b + i; q.fkey[at] = batch_key(q, unit, s_fk[i]); q.fprev[at] = s_fp[i]; }
-            f.n_fol = 0;
-        }
-    }
-    m = __ballot(q_cd);
-    if (!STAGE_CAND) {
-        // candidates are rare (~1e-4 of the hits): one aggregated atomic per batch that holds any
-        if (m) {
-            unsigned long long b = 0;
-            if (lane == (uint32_t)__builtin_ctzll(m)) b = atomicAdd(&q.ctr->ncand, (unsigned long long)__popcll(m));
-            b = __shfl(b, __builtin_ctzll(m));
-            const unsigned long long i = b + __popcll(m & lt_mask);
-            if (q_cd && i < q.cand_cap) { r_cd.unit = unit; q.cand[i] = r_cd; }
-        }
-    } else if (m || (final && f.n_cd)) {
-        const uint32_t add = (uint32_t)__popcll(m);
-        if (f.n_cd + add > (uint32_t)QCAP || (final && !m)) {
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(&q.ctr->ncand, (unsigned long long)f.n_cd);
-            b = __shfl(b, 0);
-            if (lane < f.n_cd && b + lane < q.cand_cap) { Cand c = s_cd[lane]; c.unit = unit; q.cand[b + lane] = c; }
-            f.n_cd = 0;
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (q_cd) s_cd[f.n_cd + __popcll(m & lt_mask)] = r_cd;
-        f.n_cd += add;
-        if (final && f.n_cd) {
-            __builtin_amdgcn_wave_barrier();
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(&q.ctr->ncand, (unsigned long long)f.n_cd);
-            b = __shfl(b, 0);
-            if (lane < f.n_cd && b + lane < q.cand_cap) { Cand c = s_cd[lane]; c.unit = unit; q.cand[b + lane] = c; }
-            f.n_cd = 0;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-}
+// ---- what the exact walks produce: records for the batch's queues ----------------------------------------------------
+// walk_hit, the walks of k4_extend_generic and wave_extend_record below classify a hit; what it leaves — a follower, a hit
+// for the next walk kernel, a candidate — is appended through WaveQueue (k4_queue.h): the records of one kind wait in a
+// wave-private LDS array, push(pred, record) takes those of a whole wavefront and flushes when they would not fit, one atomic
+// per flush, and a sink per queue names the counter, the capacity, the shard and how a record is stored (the batch key of a
+// follower staged by walk_hit and the unit of a generic-walk hit are added there).
 
 // ---- wave-cooperative walk: 64 bases per step ---------------------------------------------
 struct WalkResult {
@@ -864,8 +739,7 @@ __device__ WalkResult wave_walk_fast(const GStrandView &T, const GStrandView &Q,
 // full extension of one hit by one wavefront: what it leaves (valid in lane 0) — nothing, a follower record or a candidate
 struct HitRecord {
     int kind;   // 0 nothing, 1 follower, 2 candidate
-    uint64_t fkey;
-    uint32_t fprev;
+    FollowRec f;
     Cand c;
 };
 __device__ __forceinline__ HitRecord wave_extend_record(const GStrandView &T, const GStrandView &Q, uint2 h, int xdrop, int hspthresh,
@@ -877,8 +751,7 @@ __device__ __forceinline__ HitRecord wave_extend_record(const GStrandView &T, co
                           : wave_walk_fast(T, Q, et, d, -1, (uint32_t)min(et, eq), xdrop);
     if (L.found) {
         out.kind = 1;
-        out.fkey = follow_key(q, unit, d, Q.len, (uint32_t)et);
-        out.fprev = L.prev_end;
+        out.f = FollowRec{follow_key(q, unit, d, Q.len, (uint32_t)et), L.prev_end};
         return out;
     }
     WalkResult R = wave_walk_fast(T, Q, et, d, +1, min(T.len - (uint32_t)et, Q.len - (uint32_t)eq), xdrop);
@@ -891,61 +764,6 @@ __device__ __forceinline__ HitRecord wave_extend_record(const GStrandView &T, co
     }
     return out;
 }
-// A wavefront's records, kept in LDS until 16 are waiting: a same-address atomic takes ~13 ns, a C5 batch has 3 * 10^6 long
-// hits and as many large segments, and every one of them leaves records: one atomic per queue and 16 records instead
-constexpr uint32_t STAGE = 16;
-struct WaveStage {
-    Cand c[STAGE];
-    uint64_t fk[STAGE];
-    uint32_t fp[STAGE];
-};
-__device__ __forceinline__ void stage_flush(WaveStage &S, uint32_t &nf, uint32_t &nc, const ExtQueues &q) {
-    const uint32_t lane = threadIdx.x & 63u;
-    __builtin_amdgcn_wave_barrier();   // lane 0's records, read by the other lanes of this wavefront
-    if (nf) {
-        unsigned long long i = 0;
-        if (lane == 0) i = atomicAdd(&q.ctr->nfollow8[queue_shard()], (unsigned long long)nf);
-        i = __shfl(i, 0) + lane;
-        if (lane < nf && i < q.follow_cap) {
-            i += (unsigned long long)queue_shard() * q.follow_cap;
-            q.fkey[i] = S.fk[lane];
-            q.fprev[i] = S.fp[lane];
-        }
-    }
-    if (nc) {
-        unsigned long long i = 0;
-        if (lane == 0) i = atomicAdd(&q.ctr->ncand, (unsigned long long)nc);
-        i = __shfl(i, 0) + lane;
-        if (lane < nc && i < q.cand_cap) q.cand[i] = S.c[lane];
-    }
-    __builtin_amdgcn_wave_barrier();
-    nf = nc = 0;
-}
-__device__ __forceinline__ void stage_push(WaveStage &S, uint32_t &nf, uint32_t &nc, const HitRecord &r, const ExtQueues &q) {
-    const int kind = __builtin_amdgcn_readfirstlane(r.kind);
-    if (kind == 1) { if ((threadIdx.x & 63u) == 0) { S.fk[nf] = r.fkey; S.fp[nf] = r.fprev; } nf++; }
-    else if (kind == 2) { if ((threadIdx.x & 63u) == 0) S.c[nc] = r.c; nc++; }
-    if (nf == STAGE || nc == STAGE) stage_flush(S, nf, nc, q);
-}
-
-// ... or appended at once (lane 0)
-__device__ __forceinline__ void wave_extend_emit(const GStrandView &T, const GStrandView &Q, uint2 h, int xdrop, int hspthresh,
-                                                 int transitions, bool detect, const ExtQueues &q, uint32_t unit, uint32_t *rext_out) {
-    const HitRecord r = wave_extend_record(T, Q, h, xdrop, hspthresh, transitions, detect, q, unit, rext_out);
-    if ((threadIdx.x & 63) != 0) return;
-    if (r.kind == 1) {
-        unsigned long long i = atomicAdd(&q.ctr->nfollow8[queue_shard()], 1ull);
-        if (i < q.follow_cap) {
-            i += (unsigned long long)queue_shard() * q.follow_cap;
-            q.fkey[i] = r.fkey;
-            q.fprev[i] = r.fprev;
-        }
-    } else if (r.kind == 2) {
-        unsigned long long i = atomicAdd(&q.ctr->ncand, 1ull);
-        if (i < q.cand_cap) q.cand[i] = r.c;
-    }
-}
-
 // per-lane walk without seed detection, windows loaded on demand; false = still alive after
 // LONG_WINDOWS windows (the caller hands the work to a wavefront)
 __device__ __forceinline__ bool lane_walk(const uint32_t *__restrict__ tab, const GStrandView &T, const GStrandView &Q,

@@ -28,7 +28,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "k4_device.h"
+#include "k4_queue.h"
 
 namespace mimeo {
 
@@ -39,66 +39,29 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_extend_generic(const UnitDesc 
     __shared__ uint32_t tab[GROUP_TAB];
     for (int i = threadIdx.x; i < GROUP_TAB; i += EXT_THREADS) tab[i] = group_tab[i];
     __syncthreads();
-    // the hits come in eight shards (counts produced by the heavy kernels): sh_end[r] = hits in shards 0 .. r
-    uint64_t sh_end[8];
-    {
-        uint64_t acc = 0;
-#pragma unroll
-        for (int r = 0; r < 8; r++) { acc += min((uint64_t)q.ctr->nmed8[r], q.med_cap); sh_end[r] = acc; }
-    }
-    const uint64_t nhits = sh_end[7];
+    const ShardMap hits(q.ctr->nmed8, q.med_cap);   // the hits come in eight shards (counts produced by the heavy kernels)
+    const uint64_t nhits = hits.total();
     // What a hit leaves — a follower record, a place in the long queue or a candidate — waits in LDS until the wavefront has 64
     // of a kind: appended lane by lane where the walks end, these were three same-address atomics per wavefront and step
     // (~13 ns each: the duration of this kernel on a batch with 3 * 10^7 such hits)
-    constexpr uint32_t GCAP = 64;
-    __shared__ uint64_t s_fk[EXT_THREADS / 64][GCAP];
-    __shared__ uint32_t s_fp[EXT_THREADS / 64][GCAP];
-    __shared__ uint2 s_lh[EXT_THREADS / 64][GCAP];
-    __shared__ uint32_t s_lu[EXT_THREADS / 64][GCAP];
-    __shared__ Cand s_cd[EXT_THREADS / 64][GCAP];
+    constexpr int GCAP = 64;
+    __shared__ FollowerSink<>::Lds<GCAP> s_fol[EXT_THREADS / 64];
+    __shared__ LongSink::Lds<GCAP> s_long[EXT_THREADS / 64];
+    __shared__ CandSink::Lds<GCAP> s_cd[EXT_THREADS / 64];
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    uint32_t n_fol = 0, n_long = 0, n_cd = 0;   // wave-uniform
-    auto flush_fol = [&]() {
-        __builtin_amdgcn_wave_barrier();
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(&q.ctr->nfollow8[queue_shard()], (unsigned long long)n_fol);
-        b = __shfl(b, 0) + lane;
-        if (lane < n_fol && b < q.follow_cap) { const size_t at = (size_t)queue_shard() * q.follow_cap + b; q.fkey[at] = s_fk[wv][lane]; q.fprev[at] = s_fp[wv][lane]; }
-        n_fol = 0;
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto flush_long = [&]() {
-        __builtin_amdgcn_wave_barrier();
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(&q.ctr->nlong, (unsigned long long)n_long);
-        b = __shfl(b, 0) + lane;
-        if (lane < n_long && b < q.long_cap) { q.longq[b] = s_lh[wv][lane]; q.longu[b] = s_lu[wv][lane]; }
-        n_long = 0;
-        __builtin_amdgcn_wave_barrier();
-    };
-    auto flush_cd = [&]() {
-        __builtin_amdgcn_wave_barrier();
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(&q.ctr->ncand, (unsigned long long)n_cd);
-        b = __shfl(b, 0) + lane;
-        if (lane < n_cd && b < q.cand_cap) q.cand[b] = s_cd[wv][lane];
-        n_cd = 0;
-        __builtin_amdgcn_wave_barrier();
-    };
+    WaveQueue<FollowerSink<>, GCAP> fol(FollowerSink<>{q, 0u}, s_fol[wv]);
+    WaveQueue<LongSink, GCAP> lng(LongSink{q}, s_long[wv]);
+    WaveQueue<CandSink, GCAP> cd(CandSink{q}, s_cd[wv]);
     const uint64_t stride = (uint64_t)gridDim.x * EXT_THREADS;
     for (uint64_t g0 = (uint64_t)blockIdx.x * EXT_THREADS + wv * 64u; g0 < nhits; g0 += stride) {   // wave-uniform bound
         const uint64_t gid = g0 + lane;
         bool o_fol = false, o_long = false, o_cd = false;
-        uint64_t r_fk = 0;
-        uint32_t r_fp = 0, unit = 0;
+        FollowRec r_f{0, 0};
+        uint32_t unit = 0;
         uint2 h = make_uint2(0, 0);
         Cand r_cd{0, 0, 0, 0, 0};
         if (gid < nhits) {
-            uint32_t r = 0;
-#pragma unroll
-            for (int k = 0; k < 7; k++) r += gid >= sh_end[k] ? 1u : 0u;
-            const uint64_t at = (uint64_t)r * q.med_cap + (gid - (r ? sh_end[r - 1] : 0));
+            const uint64_t at = hits.slot(gid);
             const uint4 rec = q.medq[at];
             h = make_uint2(rec.x, rec.y);
             unit = q.medu[at];
@@ -141,8 +104,8 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_extend_generic(const UnitDesc 
             }
             if (!is_long && L.found) {
                 o_fol = true;
-                r_fk = follow_key(q, unit, d, Q.len, (uint32_t)et);
-                r_fp = (uint32_t)et - L.found_step;  // position of the base just summed = that seed's end
+                r_f.key = follow_key(q, unit, d, Q.len, (uint32_t)et);
+                r_f.prev = (uint32_t)et - L.found_step;  // position of the base just summed = that seed's end
             } else {
                 // ---- right walk: from the seed end, or (right alive) from the record
                 WalkState R{rs.kind ? rs.run : 0, rs.kind ? rs.best : 0, rs.kind ? rs.bk : 0u, rs.kind ? FRAME_STEPS : 0u, false, false, 0};
@@ -162,31 +125,13 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_extend_generic(const UnitDesc 
                 }
             }
         }
-        uint64_t m = __ballot(o_fol);
-        if (m) {
-            const uint32_t add = (uint32_t)__popcll(m);
-            if (n_fol + add > GCAP) flush_fol();
-            if (o_fol) { const uint32_t i = n_fol + (uint32_t)__popcll(m & lt_mask); s_fk[wv][i] = r_fk; s_fp[wv][i] = r_fp; }
-            n_fol += add;
-        }
-        m = __ballot(o_long);
-        if (m) {
-            const uint32_t add = (uint32_t)__popcll(m);
-            if (n_long + add > GCAP) flush_long();
-            if (o_long) { const uint32_t i = n_long + (uint32_t)__popcll(m & lt_mask); s_lh[wv][i] = h; s_lu[wv][i] = unit; }
-            n_long += add;
-        }
-        m = __ballot(o_cd);
-        if (m) {
-            const uint32_t add = (uint32_t)__popcll(m);
-            if (n_cd + add > GCAP) flush_cd();
-            if (o_cd) s_cd[wv][n_cd + (uint32_t)__popcll(m & lt_mask)] = r_cd;
-            n_cd += add;
-        }
+        fol.push(o_fol, r_f);
+        lng.push(o_long, LongRec{h, unit});
+        cd.push(o_cd, r_cd);
     }
-    if (n_fol) flush_fol();
-    if (n_long) flush_long();
-    if (n_cd) flush_cd();
+    fol.flush();
+    lng.flush();
+    cd.flush();
 }
 
 // ---- heavy kernel of the A/B path: the hit array of the stand-alone K3 join, one lane per hit ----------------
@@ -204,59 +149,47 @@ __device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GSt
     constexpr int SCAP = 256;   // staged followers per wavefront: one same-address atomic per 256 records
     constexpr int MCAP = 128;   // ... and generic-walk records, 16 bytes each with the walk's state: the 16 KiB that 256 bare hits took
     // nhits_dev: the hits are the walk queue of this unit, filled by K34 just before on the same stream: eight shards of
-    // capacity `nhits` each, the counts on the device.  sh_end[r] = hits in shards 0 .. r.
-    uint64_t sh_end[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const uint64_t shard_cap = nhits;
-    if (nhits_dev) {
-        uint64_t acc = 0;
-#pragma unroll
-        for (int r = 0; r < 8; r++) { acc += min((uint64_t)nhits_dev[r], shard_cap); sh_end[r] = acc; }
-        nhits = acc;
-    }
+    // capacity `nhits` each, the counts on the device
+    const ShardMap walkq = nhits_dev ? ShardMap(nhits_dev, nhits) : ShardMap();
+    if (nhits_dev) nhits = walkq.total();
     __shared__ uint32_t tab[GROUP_TAB];
-    __shared__ uint4 s_med[FAST_THREADS / 64][MCAP];
-    __shared__ uint64_t s_fk[FAST_THREADS / 64][SCAP];
-    __shared__ uint32_t s_fp[FAST_THREADS / 64][SCAP];
-    __shared__ Cand s_cd[FAST_THREADS / 64][QCAP];
+    __shared__ GenericSink::Lds<MCAP> s_med[FAST_THREADS / 64];
+    __shared__ FollowerSink<true>::Lds<SCAP> s_fol[FAST_THREADS / 64];
+    __shared__ CandSink::Lds<QCAP> s_cd[FAST_THREADS / 64];
     __shared__ uint2 s_walk[FILTER ? FAST_THREADS / 64 : 1][QCAP];  // hits that passed the pre-filter, per wavefront
     for (int i = threadIdx.x; i < GROUP_TAB; i += FAST_THREADS) tab[i] = group_tab[i];
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
-    WaveFill fill{0, 0, 0};
+    WaveQueue<GenericSink, MCAP> med(GenericSink{q, unit}, s_med[wv]);
+    WaveQueue<FollowerSink<true>, SCAP> fol(FollowerSink<true>{q, unit}, s_fol[wv]);
+    WaveQueue<CandSink, QCAP> cd(CandSink{q}, s_cd[wv]);
     uint32_t n_walk = 0, n_walked = 0;  // wave-uniform fill levels
 
-    auto walk_batch = [&](bool active, uint2 h, bool final) {
+    auto walk_batch = [&](bool active, uint2 h) {
         bool q_med = false, q_fol = false, q_cd = false;
-        uint64_t r_fk = 0;
-        uint32_t r_fp = 0;
+        FollowRec r_f{0, 0};
         Cand r_cd{0, 0, 0, 0, 0};
         uint2 r_st = make_uint2(0, 0);
-        if (active) walk_hit<1>(tab, T, Q, h, xdrop, hspthresh, transitions, q_med, r_st, q_fol, q_cd, r_fk, r_fp, r_cd);
-        stage_records<true, SCAP, MCAP>(q, unit, s_med[wv], s_fk[wv], s_fp[wv], s_cd[wv], fill, q_med, h, r_st, q_fol, r_fk, r_fp, q_cd, r_cd, final);
+        if (active) walk_hit(tab, T, Q, h, xdrop, hspthresh, transitions, q_med, r_st, q_fol, q_cd, r_f, r_cd);
+        r_cd.unit = unit;
+        med.push(q_med, make_uint4(h.x, h.y, r_st.x, r_st.y));
+        fol.push(q_fol, r_f);
+        cd.push(q_cd, r_cd);
     };
 
     const uint64_t stride = (uint64_t)gridDim.x * FAST_THREADS;
     for (uint64_t g0 = (uint64_t)blockIdx.x * FAST_THREADS + wv * 64u; g0 < nhits; g0 += stride) {
         const uint64_t gid = g0 + lane;
         uint2 h = make_uint2(0, 0);
-        if (gid < nhits) {
-            uint64_t at = gid;
-            if (nhits_dev) {   // flat index -> (shard, index in the shard)
-                uint32_t r = 0;
-#pragma unroll
-                for (int k = 0; k < 7; k++) r += gid >= sh_end[k] ? 1u : 0u;
-                at = (uint64_t)r * shard_cap + (gid - (r ? sh_end[r - 1] : 0));
-            }
-            h = hits[at];
-        }
+        if (gid < nhits) h = hits[nhits_dev ? walkq.slot(gid) : gid];
         // a walk-queue entry that K34's first pass has put through its sharp filter already (WALK_SHARP_DONE) is not filtered
         // again; the mark comes off before anything else uses the position
         const bool marked = nhits_dev && (h.x & WALK_SHARP_DONE) != 0;
         if (nhits_dev) h.x &= POS_MASK;
         const bool valid = gid < nhits && !(skip_diag0 && h.x == h.y);  // the main diagonal of a self unit belongs to k4_diag0
         if (!FILTER) {
-            walk_batch(valid, h, false);
+            walk_batch(valid, h);
         } else {
             bool need = valid && marked;
             // (no lane with an unmarked entry — every wavefront of a queue the first pass filled alone: the filter and its
@@ -272,7 +205,7 @@ __device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GSt
                 if (n_walk + add > (uint32_t)QCAP) {  // walk what is queued (nearly a full wavefront), then queue
                     __builtin_amdgcn_wave_barrier();
                     const uint2 hq = s_walk[wv][lane < n_walk ? lane : 0];
-                    walk_batch(lane < n_walk, hq, false);
+                    walk_batch(lane < n_walk, hq);
                     n_walked += n_walk;
                     n_walk = 0;
                     __builtin_amdgcn_wave_barrier();
@@ -285,7 +218,7 @@ __device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GSt
     if (FILTER && n_walk) {
         __builtin_amdgcn_wave_barrier();
         const uint2 hq = s_walk[wv][lane < n_walk ? lane : 0];
-        walk_batch(lane < n_walk, hq, false);
+        walk_batch(lane < n_walk, hq);
         n_walked += n_walk;
     }
     // the statistic: one atomic per WORKGROUP (a same-address atomic serialises at ~13 ns: one per wavefront was 13 us of a
@@ -298,7 +231,9 @@ __device__ __forceinline__ void extend_hits_body(const GStrandView &T, const GSt
         __syncthreads();
         if (threadIdx.x == 0 && s_nwalked) atomicAdd(&q.ctr->nwalked, (unsigned long long)s_nwalked);
     }
-    walk_batch(false, make_uint2(0, 0), true);  // flush the staged records
+    med.flush();
+    fol.flush();
+    cd.flush();
     if (!nhits_dev && blockIdx.x == 0 && threadIdx.x == 0) q.unit_hits[unit] = nhits;
 }
 // the hit array of ONE unit (A/B path: K3's join)
@@ -335,39 +270,31 @@ __global__ __launch_bounds__(256) void k4_walk_summary(const FusedUnit *__restri
 
 // ---- long hits, one wavefront each ------------------------------------------------------------------------
 // (three wavefronts per SIMD fit its registers; the hits differ in length by orders of magnitude — a microsatellite diagonal
-// against a few hundred bases — so a wavefront takes the next 16 hits from a counter instead of a fixed stride; records: WaveStage)
+// against a few hundred bases — so a wavefront takes the next 16 hits from a counter instead of a fixed stride; records: RecordStage)
 constexpr uint32_t CLAIM = 16;
 __global__ __launch_bounds__(EXT_THREADS) void k4_extend_long(const UnitDesc *__restrict__ units, ExtQueues q, int xdrop,
                                                               int hspthresh, int transitions) {
-    __shared__ WaveStage s_stage[EXT_THREADS / 64];
-    WaveStage &S = s_stage[threadIdx.x >> 6];
-    uint32_t nf = 0, nc = 0;
+    __shared__ RecordStage::Lds s_stage[EXT_THREADS / 64];
+    RecordStage S(q, s_stage[threadIdx.x >> 6]);
     const uint64_t nlong = min((uint64_t)q.ctr->nlong, q.long_cap);
     for (;;) {
-        unsigned long long w0 = 0;
-        if ((threadIdx.x & 63u) == 0) w0 = atomicAdd(&q.ctr->long_next, (unsigned long long)CLAIM);
-        w0 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w0);
+        const uint64_t w0 = wave_claim(&q.ctr->long_next, CLAIM);
         if (w0 >= nlong) break;
-        for (uint64_t wid = w0; wid < min(nlong, (uint64_t)w0 + CLAIM); wid++) {
+        for (uint64_t wid = w0; wid < min(nlong, w0 + CLAIM); wid++) {
             const uint32_t unit = q.longu[wid];
-            stage_push(S, nf, nc, wave_extend_record(units[unit].T, units[unit].Q, q.longq[wid], xdrop, hspthresh, transitions, true, q, unit, nullptr), q);
+            S.push(wave_extend_record(units[unit].T, units[unit].Q, q.longq[wid], xdrop, hspthresh, transitions, true, q, unit, nullptr));
         }
     }
-    stage_flush(S, nf, nc, q);
+    S.flush();
 }
 
 // ---- the follower shards gathered into one array (input of the sort) ---------------------------------------------
 __global__ __launch_bounds__(256) void k4_compact_followers(ExtQueues q, uint64_t *__restrict__ key, uint32_t *__restrict__ prev) {
-    uint64_t sh_end[8];
-    uint64_t acc = 0;
-#pragma unroll
-    for (int r = 0; r < 8; r++) { acc += min((uint64_t)q.ctr->nfollow8[r], q.follow_cap); sh_end[r] = acc; }
-    if (blockIdx.x == 0 && threadIdx.x == 0) q.ctr->nfollow = acc;
-    for (uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x; gid < acc; gid += (uint64_t)gridDim.x * 256) {
-        uint32_t r = 0;
-#pragma unroll
-        for (int k = 0; k < 7; k++) r += gid >= sh_end[k] ? 1u : 0u;
-        const uint64_t at = (uint64_t)r * q.follow_cap + (gid - (r ? sh_end[r - 1] : 0));
+    const ShardMap fol(q.ctr->nfollow8, q.follow_cap);
+    const uint64_t n = fol.total();
+    if (blockIdx.x == 0 && threadIdx.x == 0) q.ctr->nfollow = n;
+    for (uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x; gid < n; gid += (uint64_t)gridDim.x * 256) {
+        const uint64_t at = fol.slot(gid);
         key[gid] = q.fkey[at];
         prev[gid] = q.fprev[at];
     }
@@ -441,10 +368,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_resolve_small(const UnitDesc *
         bigseg[wave_slot(&q.ctr->nbig)] = sid;
         return;
     }
-    for (uint32_t k = 0; k < nout; k++) {
-        const unsigned long long i = wave_slot(&q.ctr->ncand);
-        if (i < q.cand_cap) q.cand[i] = out[k];
-    }
+    for (uint32_t k = 0; k < nout; k++) append_now(CandSink{q}, out[k]);
 }
 
 // one wavefront per segment: replay "skip while seed end <= reach, else extend" (lastz diagEnd rule)
@@ -456,67 +380,64 @@ __global__ __launch_bounds__(EXT_THREADS) void k4_resolve_segments(const UnitDes
                                                                    const uint64_t *__restrict__ list, int xdrop,
                                                                    int hspthresh, int transitions) {
     const uint64_t nseg = *nseg_dev, nlist = q.ctr->nbig;
-    __shared__ WaveStage s_stage[EXT_THREADS / 64];
-    WaveStage &S = s_stage[threadIdx.x >> 6];
-    uint32_t nf = 0, nc = 0;
+    __shared__ RecordStage::Lds s_stage[EXT_THREADS / 64];
+    RecordStage S(q, s_stage[threadIdx.x >> 6]);
     for (;;) {   // segments differ in size by orders of magnitude: the next 16 from a counter
-    unsigned long long w0 = 0;
-    if ((threadIdx.x & 63) == 0) w0 = atomicAdd(&q.ctr->seg_next, (unsigned long long)CLAIM);
-    w0 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w0);
-    if (w0 >= nlist) break;
-    // the heads of the 16 segments, one per lane: four dependent loads for all of them instead of four for each
-    uint64_t l_beg = 0, l_end = 0, l_k0 = 0;
-    uint32_t l_het = 0;
-    if ((threadIdx.x & 63u) < CLAIM && w0 + (threadIdx.x & 63u) < nlist) {
-        const uint64_t sid = list[w0 + (threadIdx.x & 63u)];
-        l_beg = seg_start[sid];
-        l_end = sid + 1 < nseg ? seg_start[sid + 1] : nfollow;
-        l_k0 = key[l_beg];
-        l_het = prev[l_beg];
-    }
-    for (uint64_t wid = w0; wid < min(nlist, (uint64_t)w0 + CLAIM); wid++) {
-    const int src = (int)(wid - w0);
-    uint64_t beg = __shfl(l_beg, src), end = __shfl(l_end, src);
-    uint64_t k0 = __shfl(l_k0, src);
-    const uint32_t unit = key_unit(q, k0);
-    const GStrandView T = units[unit].T, Q = units[unit].Q;
-    const int32_t d = key_diag(q, k0, Q.len);
-    // head: seed end = prev[beg]; only its right extent matters (it was emitted by the heavy kernel or the walks)
-    int32_t het = (int32_t)__shfl(l_het, src);
-    WalkResult R = wave_walk_fast(T, Q, het, d, +1, min(T.len - (uint32_t)het, Q.len - (uint32_t)(het - d)), xdrop);
-    uint32_t reach = (uint32_t)het + R.bsteps;
-    uint64_t i = beg;
-    while (i < end) {
-        // first record at or after i that reaches beyond `reach` (records are sorted by seed end; a RUN_END record stands for
-        // every position behind the record before it up to its own)
-        // (the next 64 records in one load, lane by lane — most segments end there; a binary search, one memory round trip per
-        // step, only behind them)
-        uint64_t nxt;
-        {
-            const uint64_t x = i + (threadIdx.x & 63u);
-            const uint64_t m = __ballot(x < end && key_end(q, key[x]) > reach);
-            if (m) nxt = i + (uint64_t)__builtin_ctzll(m);
-            else {
-                uint64_t lo = min(end, i + 64u), hi = end;
-                while (lo < hi) {
-                    uint64_t mid = (lo + hi) >> 1;
-                    if (key_end(q, key[mid]) > reach) hi = mid; else lo = mid + 1;
+        const uint64_t w0 = wave_claim(&q.ctr->seg_next, CLAIM);
+        if (w0 >= nlist) break;
+        // the heads of the 16 segments, one per lane: four dependent loads for all of them instead of four for each
+        uint64_t l_beg = 0, l_end = 0, l_k0 = 0;
+        uint32_t l_het = 0;
+        if ((threadIdx.x & 63u) < CLAIM && w0 + (threadIdx.x & 63u) < nlist) {
+            const uint64_t sid = list[w0 + (threadIdx.x & 63u)];
+            l_beg = seg_start[sid];
+            l_end = sid + 1 < nseg ? seg_start[sid + 1] : nfollow;
+            l_k0 = key[l_beg];
+            l_het = prev[l_beg];
+        }
+        for (uint64_t wid = w0; wid < min(nlist, w0 + CLAIM); wid++) {
+            const int src = (int)(wid - w0);
+            uint64_t beg = __shfl(l_beg, src), end = __shfl(l_end, src);
+            uint64_t k0 = __shfl(l_k0, src);
+            const uint32_t unit = key_unit(q, k0);
+            const GStrandView T = units[unit].T, Q = units[unit].Q;
+            const int32_t d = key_diag(q, k0, Q.len);
+            // head: seed end = prev[beg]; only its right extent matters (it was emitted by the heavy kernel or the walks)
+            int32_t het = (int32_t)__shfl(l_het, src);
+            WalkResult R = wave_walk_fast(T, Q, het, d, +1, min(T.len - (uint32_t)het, Q.len - (uint32_t)(het - d)), xdrop);
+            uint32_t reach = (uint32_t)het + R.bsteps;
+            uint64_t i = beg;
+            while (i < end) {
+                // first record at or after i that reaches beyond `reach` (records are sorted by seed end; a RUN_END record stands for
+                // every position behind the record before it up to its own)
+                // (the next 64 records in one load, lane by lane — most segments end there; a binary search, one memory round trip per
+                // step, only behind them)
+                uint64_t nxt;
+                {
+                    const uint64_t x = i + (threadIdx.x & 63u);
+                    const uint64_t m = __ballot(x < end && key_end(q, key[x]) > reach);
+                    if (m) nxt = i + (uint64_t)__builtin_ctzll(m);
+                    else {
+                        uint64_t lo = min(end, i + 64u), hi = end;
+                        while (lo < hi) {
+                            uint64_t mid = (lo + hi) >> 1;
+                            if (key_end(q, key[mid]) > reach) hi = mid; else lo = mid + 1;
+                        }
+                        nxt = lo;
+                    }
                 }
-                nxt = lo;
+                if (nxt >= end) break;
+                uint32_t et = key_end(q, key[nxt]);
+                if (prev[nxt] == RUN_END) et = max(key_end(q, key[nxt - 1]) + 1u, reach + 1u);   // the first member of the run beyond the reach
+                uint2 h = make_uint2(et - SEED_LEN, (uint32_t)((int32_t)et - d) - SEED_LEN);
+                uint32_t rext = 0;
+                S.push(wave_extend_record(T, Q, h, xdrop, hspthresh, transitions, false, q, unit, &rext));
+                reach = et + rext;
+                i = nxt;   // the same record again: a run may hold more members beyond the new reach (a plain record is passed by the search)
             }
         }
-        if (nxt >= end) break;
-        uint32_t et = key_end(q, key[nxt]);
-        if (prev[nxt] == RUN_END) et = max(key_end(q, key[nxt - 1]) + 1u, reach + 1u);   // the first member of the run beyond the reach
-        uint2 h = make_uint2(et - SEED_LEN, (uint32_t)((int32_t)et - d) - SEED_LEN);
-        uint32_t rext = 0;
-        stage_push(S, nf, nc, wave_extend_record(T, Q, h, xdrop, hspthresh, transitions, false, q, unit, &rext), q);
-        reach = et + rext;
-        i = nxt;   // the same record again: a run may hold more members beyond the new reach (a plain record is passed by the search)
     }
-    }
-    }
-    stage_flush(S, nf, nc, q);
+    S.flush();
 }
 
 // ---- the main diagonal of a strand aligned to itself ---------------------------------------------------------
@@ -563,119 +484,108 @@ __global__ __launch_bounds__(64) void k4_diag0(const UnitDesc *__restrict__ unit
 constexpr uint32_t ENT_LANES = 8;
 constexpr uint32_t ENT_LONG = 1u << 16;     // columns: longer candidates (the main diagonal of a self unit: the whole scaffold) ...
 constexpr uint32_t ENT_BIGCAP = 4096;       // ... are counted by the whole grid (k4_entropy_big), up to this many per batch
-constexpr uint32_t ENT_STAGE = 64;   // HSPs a wavefront collects before it appends them (8 per step at most)
-__device__ __forceinline__ void entropy_flush(const mimeo_hsp *sh, const uint32_t *su, uint32_t &n, const ExtQueues &q, mimeo_hsp *__restrict__ out,
-                                              uint32_t *__restrict__ out_unit) {
-    __builtin_amdgcn_wave_barrier();
-    if (n) {
-        const uint32_t lane = threadIdx.x & 63u;
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(&q.ctr->nhsp, (unsigned long long)n);
-        b = __shfl(b, 0);
-        if (lane < n) { out[b + lane] = sh[lane]; out_unit[b + lane] = su[lane]; }
-    }
-    __builtin_amdgcn_wave_barrier();
-    n = 0;
+constexpr int ENT_STAGE = 64;        // HSPs a wavefront collects before it appends them (8 per step at most)
+
+// the columns of 32 consecutive positions of a gap-free segment; valid: the positions that belong to it
+__device__ __forceinline__ uint32_t valid_columns(uint32_t rem) { return rem < 32 ? (1u << rem) - 1u : 0xFFFFFFFFu; }
+// ... the identical ones, per base
+template <class C>
+__device__ __forceinline__ void column_counts(const Win32 &tw, const Win32 &qw, uint32_t valid, C (&cnt)[4]) {
+    const uint32_t m = valid & ~((tw.lo ^ qw.lo) | (tw.hi ^ qw.hi)) & ~(tw.nm | qw.nm);
+    cnt[0] += __popc(m & ~tw.lo & ~tw.hi);
+    cnt[1] += __popc(m & tw.lo & ~tw.hi);
+    cnt[2] += __popc(m & ~tw.lo & tw.hi);
+    cnt[3] += __popc(m & tw.lo & tw.hi);
 }
+// ... and their HOXD70 sum, for a segment whose score does not fit 32 bits (RAW_SATURATED)
+__device__ __forceinline__ int64_t column_score64(const Win32 &tw, const Win32 &qw, uint32_t valid) {
+    const uint32_t nn = (tw.nm | qw.nm) & valid, ok = valid & ~nn, dl = (tw.lo ^ qw.lo) & ok, dh = (tw.hi ^ qw.hi) & ok;
+    const uint32_t cg = tw.lo ^ tw.hi;
+    return 91ll * __popc(ok) + 9ll * __popc(ok & ~(dl | dh) & cg) - 122ll * __popc(~dl & dh) - 205ll * __popc(dl) - 9ll * __popc(dl & dh) -
+           2ll * __popc(dl & dh & cg) - 100ll * __popc(nn);
+}
+// lastz's --entropy: the raw score times the Shannon entropy (base 4) of the identical columns' bases, in 1/65536
+template <class C>
+__device__ __forceinline__ int64_t entropy_adjust(int64_t raw, const C (&cnt)[4], int entropy) {
+    if (!entropy) return raw;
+    const uint64_t n = (uint64_t)cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    double hh = 0.0;
+    if (n) {
+        for (int b = 0; b < 4; b++)
+            if (cnt[b]) { double p = (double)cnt[b] / (double)n; hh -= p * log(p); }
+        hh /= log(4.0);
+    }
+    int64_t q16 = (int64_t)floor(hh * 65536.0 + 0.5);
+    q16 = q16 > 65536 ? 65536 : (q16 < 0 ? 0 : q16);
+    return (raw * q16) >> 16;
+}
+__device__ __forceinline__ HspRec make_hsp(const Cand &c, int64_t adj, int64_t raw) {
+    mimeo_hsp h;
+    h.tstart = c.tstart; h.qstart = c.qstart; h.length = c.len; h.flags = 0; h.score = adj; h.raw_score = raw;
+    return HspRec{h, c.unit};
+}
+
 __global__ __launch_bounds__(EXT_THREADS) void k4_entropy(const UnitDesc *__restrict__ units, ExtQueues q, int hspthresh,
                                                           int entropy, mimeo_hsp *__restrict__ out,
                                                           uint32_t *__restrict__ out_unit) {
-    __shared__ mimeo_hsp s_h[EXT_THREADS / 64][ENT_STAGE];
-    __shared__ uint32_t s_u[EXT_THREADS / 64][ENT_STAGE];
-    const uint32_t wv = threadIdx.x >> 6;
-    uint32_t nstage = 0;
+    // The HSPs wait in LDS until the wavefront has 64 of them: one atomic per wavefront and STEP was 2.5 * 10^6 same-address
+    // atomics for the 2.7 * 10^7 candidates of 32 C5 units — 13 ns each, the whole duration of this kernel
+    __shared__ HspSink::Lds<ENT_STAGE> s_hsp[EXT_THREADS / 64];
+    WaveQueue<HspSink, ENT_STAGE> hsps(HspSink{q, out, out_unit}, s_hsp[threadIdx.x >> 6]);
     const uint32_t sub = threadIdx.x & (ENT_LANES - 1u);
     const uint64_t ncand = min((uint64_t)q.ctr->ncand, q.cand_cap);
     const uint64_t ngroups = ((uint64_t)gridDim.x * EXT_THREADS) / ENT_LANES;
     // the loop bound is wave-uniform (rounded up to the wavefront's eight groups): the shuffles below need every lane
     const uint64_t first = (((uint64_t)blockIdx.x * EXT_THREADS + threadIdx.x) / 64) * (64 / ENT_LANES);
     for (uint64_t base = first; base < ncand; base += ngroups) {
-    const uint64_t cid = base + (threadIdx.x & 63u) / ENT_LANES;
-    const bool live = cid < ncand;
-    Cand c = q.cand[live ? cid : ncand - 1];
-    if (!live) c.len = 0;
-    if (c.len > ENT_LONG) {   // one group of eight lanes would crawl through millions of columns with the wavefront waiting
-        unsigned long long slot = ENT_BIGCAP;
-        if (sub == 0) slot = wave_slot(&q.ctr->nbigcand);
-        slot = __shfl(slot, (int)((threadIdx.x & 63u) & ~(ENT_LANES - 1u)));
-        if (slot < ENT_BIGCAP) {
-            if (sub == 0) q.bigcand[slot] = cid;
-            c.len = 0;   // nothing to do here; k4_entropy_big emits it
-        }
-    }
-    const bool deferred = live && c.len == 0;
-    const GStrandView T = units[c.unit].T, Q = units[c.unit].Q;
-    int64_t raw = c.raw;
-    const int32_t d = (int32_t)c.tstart - (int32_t)c.qstart;
-    // the longest candidate of the wavefront sets the number of steps (wave-uniform loops: shuffles inside)
-    uint32_t maxlen = c.len;
-    for (int o = 32; o >= (int)ENT_LANES; o >>= 1) maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, o));
-    if (__ballot(c.raw == RAW_SATURATED)) {  // recount the column scores of the segment in 64 bits (rare)
-        int64_t sum = 0;
-        for (uint32_t o0 = 0; o0 < maxlen; o0 += ENT_LANES * 32u) {
-            const uint32_t o = o0 + sub * 32u;
-            if (o < c.len && c.raw == RAW_SATURATED) {
-                const int32_t pt = (int32_t)(c.tstart + o);
-                const Win32 tw = win32(T, pt), qw = win32(Q, pt - d);
-                const uint32_t rem = c.len - o, valid = rem < 32 ? (1u << rem) - 1u : 0xFFFFFFFFu;
-                const uint32_t nn = (tw.nm | qw.nm) & valid, dl = (tw.lo ^ qw.lo) & ~nn & valid, dh = (tw.hi ^ qw.hi) & ~nn & valid;
-                const uint32_t cg = tw.lo ^ tw.hi, ok = valid & ~nn;
-                sum += 91ll * __popc(ok) + 9ll * __popc(ok & ~(dl | dh) & cg) - 122ll * __popc(~dl & dh) - 205ll * __popc(dl) -
-                       9ll * __popc(dl & dh) - 2ll * __popc(dl & dh & cg) - 100ll * __popc(nn);
+        const uint64_t cid = base + (threadIdx.x & 63u) / ENT_LANES;
+        const bool live = cid < ncand;
+        Cand c = q.cand[live ? cid : ncand - 1];
+        if (!live) c.len = 0;
+        if (c.len > ENT_LONG) {   // one group of eight lanes would crawl through millions of columns with the wavefront waiting
+            unsigned long long slot = ENT_BIGCAP;
+            if (sub == 0) slot = wave_slot(&q.ctr->nbigcand);
+            slot = __shfl(slot, (int)((threadIdx.x & 63u) & ~(ENT_LANES - 1u)));
+            if (slot < ENT_BIGCAP) {
+                if (sub == 0) q.bigcand[slot] = cid;
+                c.len = 0;   // nothing to do here; k4_entropy_big emits it
             }
         }
-        for (int o = ENT_LANES / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        if (c.raw == RAW_SATURATED) raw = sum;
-    }
-    int64_t adj = raw;
-    if (entropy) {
+        const bool deferred = live && c.len == 0;
+        const GStrandView T = units[c.unit].T, Q = units[c.unit].Q;
+        int64_t raw = c.raw;
+        const int32_t d = (int32_t)c.tstart - (int32_t)c.qstart;
+        // the longest candidate of the wavefront sets the number of steps (wave-uniform loops: shuffles inside)
+        uint32_t maxlen = c.len;
+        for (int o = 32; o >= (int)ENT_LANES; o >>= 1) maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, o));
+        if (__ballot(c.raw == RAW_SATURATED)) {  // recount the column scores of the segment in 64 bits (rare)
+            int64_t sum = 0;
+            for (uint32_t o0 = 0; o0 < maxlen; o0 += ENT_LANES * 32u) {
+                const uint32_t o = o0 + sub * 32u;
+                if (o < c.len && c.raw == RAW_SATURATED) {
+                    const int32_t pt = (int32_t)(c.tstart + o);
+                    sum += column_score64(win32(T, pt), win32(Q, pt - d), valid_columns(c.len - o));
+                }
+            }
+            for (int o = ENT_LANES / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+            if (c.raw == RAW_SATURATED) raw = sum;
+        }
         uint32_t cnt[4] = {0, 0, 0, 0};
-        for (uint32_t o0 = 0; o0 < maxlen; o0 += ENT_LANES * 32u) {
-            const uint32_t o = o0 + sub * 32u;
-            if (o < c.len) {
-                const int32_t pt = (int32_t)(c.tstart + o);
-                const Win32 tw = win32(T, pt), qw = win32(Q, pt - d);
-                const uint32_t tlo = tw.lo, thi = tw.hi;
-                uint32_t m = ~((tlo ^ qw.lo) | (thi ^ qw.hi)) & ~(tw.nm | qw.nm);
-                const uint32_t rem = c.len - o;
-                if (rem < 32) m &= (1u << rem) - 1u;
-                cnt[0] += __popc(m & ~tlo & ~thi);
-                cnt[1] += __popc(m & tlo & ~thi);
-                cnt[2] += __popc(m & ~tlo & thi);
-                cnt[3] += __popc(m & tlo & thi);
+        if (entropy) {
+            for (uint32_t o0 = 0; o0 < maxlen; o0 += ENT_LANES * 32u) {
+                const uint32_t o = o0 + sub * 32u;
+                if (o < c.len) {
+                    const int32_t pt = (int32_t)(c.tstart + o);
+                    column_counts(win32(T, pt), win32(Q, pt - d), valid_columns(c.len - o), cnt);
+                }
             }
-        }
-        for (int b = 0; b < 4; b++)
-            for (int o = ENT_LANES / 2; o > 0; o >>= 1) cnt[b] += __shfl_xor(cnt[b], o);
-        uint64_t n = (uint64_t)cnt[0] + cnt[1] + cnt[2] + cnt[3];
-        double hh = 0.0;
-        if (n) {
             for (int b = 0; b < 4; b++)
-                if (cnt[b]) { double p = (double)cnt[b] / (double)n; hh -= p * log(p); }
-            hh /= log(4.0);
+                for (int o = ENT_LANES / 2; o > 0; o >>= 1) cnt[b] += __shfl_xor(cnt[b], o);
         }
-        int64_t q16 = (int64_t)floor(hh * 65536.0 + 0.5);
-        q16 = q16 > 65536 ? 65536 : (q16 < 0 ? 0 : q16);
-        adj = (raw * q16) >> 16;
+        const int64_t adj = entropy_adjust(raw, cnt, entropy);
+        hsps.push(live && !deferred && adj >= hspthresh && sub == 0, make_hsp(c, adj, raw));   // at most one HSP per candidate
     }
-    // The HSPs wait in LDS until the wavefront has 64 of them: one atomic per wavefront and STEP was 2.5 * 10^6 same-address
-    // atomics for the 2.7 * 10^7 candidates of 32 C5 units — 13 ns each, the whole duration of this kernel
-    const bool emit = live && !deferred && adj >= hspthresh && sub == 0;
-    const uint64_t em = __ballot(emit);
-    if (em) {
-        const uint32_t add = (uint32_t)__popcll(em);
-        if (nstage + add > ENT_STAGE) entropy_flush(s_h[wv], s_u[wv], nstage, q, out, out_unit);
-        if (emit) {
-            const uint32_t at = nstage + (uint32_t)__popcll(em & ((1ull << (threadIdx.x & 63u)) - 1ull));
-            mimeo_hsp h;
-            h.tstart = c.tstart; h.qstart = c.qstart; h.length = c.len; h.flags = 0; h.score = adj; h.raw_score = raw;
-            s_h[wv][at] = h;   // at most one HSP per candidate: the buffers hold cand_cap records
-            s_u[wv][at] = c.unit;
-        }
-        nstage += add;
-    }
-    }
-    entropy_flush(s_h[wv], s_u[wv], nstage, q, out, out_unit);
+    hsps.flush();
 }
 
 // the long candidates: every workgroup counts a slice (matched columns per base, and the raw score again in 64 bits
@@ -692,15 +602,9 @@ __global__ __launch_bounds__(256) void k4_entropy_big(const UnitDesc *__restrict
         for (uint64_t o = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 32u; o < c.len; o += (uint64_t)gridDim.x * 256 * 32u) {
             const int32_t pt = (int32_t)(c.tstart + o);
             const Win32 tw = win32(T, pt), qw = win32(Q, pt - d);
-            const uint32_t rem = (uint32_t)(c.len - o), valid = rem < 32 ? (1u << rem) - 1u : 0xFFFFFFFFu;
-            const uint32_t nn = (tw.nm | qw.nm) & valid, dl = (tw.lo ^ qw.lo) & ~nn & valid, dh = (tw.hi ^ qw.hi) & ~nn & valid;
-            const uint32_t cg = tw.lo ^ tw.hi, ok = valid & ~nn, m = ok & ~(dl | dh);
-            cnt[0] += __popc(m & ~tw.lo & ~tw.hi);
-            cnt[1] += __popc(m & tw.lo & ~tw.hi);
-            cnt[2] += __popc(m & ~tw.lo & tw.hi);
-            cnt[3] += __popc(m & tw.lo & tw.hi);
-            sum += 91ll * __popc(ok) + 9ll * __popc(m & cg) - 122ll * __popc(~dl & dh & ok) - 205ll * __popc(dl) -
-                   9ll * __popc(dl & dh) - 2ll * __popc(dl & dh & cg) - 100ll * __popc(nn);
+            const uint32_t valid = valid_columns((uint32_t)(c.len - o));
+            column_counts(tw, qw, valid, cnt);
+            sum += column_score64(tw, qw, valid);
         }
         if (threadIdx.x < 5) red[threadIdx.x] = 0;
         __syncthreads();
@@ -724,26 +628,9 @@ __global__ void k4_entropy_big_finish(ExtQueues q, int hspthresh, int entropy, m
     for (uint64_t bi = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; bi < nbig; bi += (uint64_t)gridDim.x * blockDim.x) {
         const Cand c = q.cand[q.bigcand[bi]];
         const unsigned long long *a = q.bigacc + bi * 5;
-        int64_t raw = c.raw == RAW_SATURATED ? (int64_t)a[4] : (int64_t)c.raw, adj = raw;
-        if (entropy) {
-            const uint64_t n = a[0] + a[1] + a[2] + a[3];
-            double hh = 0.0;
-            if (n) {
-                for (int b = 0; b < 4; b++)
-                    if (a[b]) { double p = (double)a[b] / (double)n; hh -= p * log(p); }
-                hh /= log(4.0);
-            }
-            int64_t q16 = (int64_t)floor(hh * 65536.0 + 0.5);
-            q16 = q16 > 65536 ? 65536 : (q16 < 0 ? 0 : q16);
-            adj = (raw * q16) >> 16;
-        }
-        if (adj >= hspthresh) {
-            const unsigned long long i = atomicAdd(&q.ctr->nhsp, 1ull);
-            mimeo_hsp h;
-            h.tstart = c.tstart; h.qstart = c.qstart; h.length = c.len; h.flags = 0; h.score = adj; h.raw_score = raw;
-            out[i] = h;
-            out_unit[i] = c.unit;
-        }
+        const unsigned long long cnt[4] = {a[0], a[1], a[2], a[3]};
+        const int64_t raw = c.raw == RAW_SATURATED ? (int64_t)a[4] : (int64_t)c.raw, adj = entropy_adjust(raw, cnt, entropy);
+        if (adj >= hspthresh) append_now(HspSink{q, out, out_unit}, make_hsp(c, adj, raw));
     }
 }
 
@@ -953,7 +840,7 @@ int ExtBatch::carve_queues() {
     q.bigcand = (unsigned long long *)bigcand.p; q.bigacc = (unsigned long long *)bigacc.p;
     q.unit_hits = (unsigned long long *)unit_hits.p; q.tile_hits = (unsigned long long *)tile_hits.p;
     q.walkq = (uint2 *)qbuf[Q_WALKQ].p;
-    q.cand_cap = cap_.c; q.follow_cap = cap_.f; q.med_cap = cap_.m; q.long_cap = cap_.l; q.walk_cap = 0;
+    q.cand_cap = cap_.c; q.follow_cap = cap_.f; q.med_cap = cap_.m; q.long_cap = cap_.l;
     return 0;
 }
 
@@ -1052,12 +939,9 @@ int ExtBatch::enqueue_v1() {
         if (rc) return rc;
         if (!nh) continue;
         const bool slim = !w.d.T.has_n && !w.d.Q.has_n;
-#define K4_LAUNCH(V) hipLaunchKernelGGL(k4_extend_hits<V>, dim3((uint32_t)std::min<uint64_t>((nh + FAST_THREADS - 1) / FAST_THREADS, 1024)), dim3(FAST_THREADS), 0, stream(), \
-                           w.d.T, w.d.Q, (const uint2 *)hits.p, nh, p_.xdrop, p_.hspthresh, p_.transitions, group_table_device(), *q_, u, (int)w.d.same)
-        if (sw_.k4_variant == 1) K4_LAUNCH(1);
-        else if (sw_.k4_variant == 5 || !slim) K4_LAUNCH(5);
-        else K4_LAUNCH(9);
-#undef K4_LAUNCH
+        const auto kernel = sw_.k4_variant == 1 ? k4_extend_hits<1> : sw_.k4_variant == 5 || !slim ? k4_extend_hits<5> : k4_extend_hits<9>;
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)std::min<uint64_t>((nh + FAST_THREADS - 1) / FAST_THREADS, 1024)), dim3(FAST_THREADS), 0, stream(),
+                           w.d.T, w.d.Q, (const uint2 *)hits.p, nh, p_.xdrop, p_.hspthresh, p_.transitions, group_table_device(), *q_, u, (int)w.d.same);
     }
     return 0;
 }
