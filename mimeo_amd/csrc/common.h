@@ -326,6 +326,7 @@ int regroup_hsps_device(mimeo_hsp *d_hsps, uint32_t *d_hunit, uint64_t nh, const
 int group_summary_device(const Group *d_groups, uint32_t ngroups, uint64_t out[3]);
 int overflowed_groups_device(const Group *d_groups, uint32_t ngroups, uint64_t expect, std::vector<uint3> *out);
 void release_pack_buffers();
+void release_k5_buffers();   // k5_chain.hip
 // chain + gapped extension of every group (pipeline.hip)
 int chain_gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_hsps, const uint32_t *d_hsp_unit, uint64_t nhsps,
                         const mimeo_params *p, DeviceBuf &scratch, mimeo_alignment *d_aln, float *ms_chain,

@@ -156,6 +156,7 @@ void release_pipeline_buffers() {
     g_ext.release();
     for (DeviceBuf *b : {&g_scratch, &g_aln, &g_dense, &g_groups, &g_pfirst, &g_pblocks}) b->release();
     g_pack.release();
+    release_k5_buffers();
     release_pack_buffers();
 }
 

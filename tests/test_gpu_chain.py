@@ -106,6 +106,27 @@ def test_chain_kernels_on_made_up_hsps(eng, monkeypatch, mode):
     assert chained > 1000
 
 
+@pytest.mark.parametrize('large', ['wave', 'two-level'])
+def test_a_group_at_the_threshold_has_exactly_one_kernel(eng, monkeypatch, large):
+    """MIMEO_K5_BIG_MIN=64: a group of exactly 64 HSPs is the tile kernel's, one of 65 the large-group kernel's (the wave kernel, or the
+    two-level kernel under MIMEO_K5_BIG=old).  The threshold reaches the list kernel and the tile kernel as one value: a group
+    claimed by neither would come back with every flag 0.  (A group claimed by both is chained twice to the same flags: this test
+    does not see that.)"""
+    from oracle import oracle as O
+    monkeypatch.delenv('MIMEO_K5_NO_BIG', raising=False)
+    monkeypatch.setenv('MIMEO_K5_BIG_MIN', '64')
+    if large == 'two-level':
+        monkeypatch.setenv('MIMEO_K5_BIG', 'old')
+    else:
+        monkeypatch.delenv('MIMEO_K5_BIG', raising=False)
+    rng = np.random.default_rng(6465)
+    for kind in ('ties', 'collinear'):
+        for n in (64, 65):
+            h = _make(kind, 90, rng)[:n]
+            assert _unique(h).size == h.size == n, (kind, n, h.size)
+            assert _check(eng, O, h, (large, kind, n)) > 0
+
+
 def test_chain_default_dispatch_on_a_large_group(eng, monkeypatch):
     """beyond 32 768 HSPs the wave kernel is the default: 40 000 of each kind, nothing set"""
     from oracle import oracle as O
@@ -116,6 +137,42 @@ def test_chain_default_dispatch_on_a_large_group(eng, monkeypatch):
         h = _make(kind, 40_000, rng)
         assert h.size > 33_000, (kind, h.size)
         assert _check(eng, O, h, (kind, 'large')) > 0
+
+
+def test_many_large_groups_in_one_batch(eng, monkeypatch):
+    """A packed self job of 16 repeat-rich scaffolds of 20 kbp, both strands: 512 groups in one batch, every one of them with two
+    or more HSPs by the oracle's gap-free stage (512 of 512 for this seed; the test needs more than 256).  The chained HSPs
+    (gapped extension off) from the default dispatch (tile kernel only: held to the oracle by test_gpu_pack.py), from the wave kernel
+    (MIMEO_K5_BIG_MIN=1: 512 workgroups, group bits of its sort keys > 8) and from the two-level kernel (MIMEO_K5_BIG=old too: a grid of
+    256 workgroups, so a workgroup loops over more than one group of its list — nowhere else in the suite) must be byte-equal.
+    (24 scaffolds of 40 kbp would be 1 152 groups; the oracle spends 0.1 s per call on its seed tables whatever the length, so the
+    count alone would take two minutes.)"""
+    from concurrent.futures import ThreadPoolExecutor
+    from mimeo_amd.synth import synth_genome
+    from oracle import oracle as O
+    ns = 16
+    names, seqs = synth_genome(31, ns * 20_000, ns, repeat_frac=0.3, families=3, cons_len=(200, 1500), max_div=0.12, microsat_frac=0.01)
+    raw = [s.tobytes() for s in seqs]
+    O.lib()
+    with ThreadPoolExecutor(16) as ex:
+        sizes = list(ex.map(lambda j: O.ungapped_hsps(raw[j[0]], raw[j[1]], j[2]).size, [(t, q, s) for t in range(ns) for q in range(ns) for s in (0, 1)]))
+    multi = sum(1 for s in sizes if s >= 2)
+    print('groups with two or more HSPs: %d of %d' % (multi, len(sizes)))
+    assert multi > 256
+    g = eng.Genome(names, seqs)
+    pairs = [(t, q) for t in range(ns) for q in range(ns)]
+    outs = {}
+    for tag, env in (('tiles', {}), ('wave', {'MIMEO_K5_BIG_MIN': '1'}), ('two-level', {'MIMEO_K5_BIG_MIN': '1', 'MIMEO_K5_BIG': 'old'})):
+        for k in ('MIMEO_K5_BIG_MIN', 'MIMEO_K5_BIG', 'MIMEO_K5_NO_BIG'):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        outs[tag] = eng.align_pairs(g, None, pairs, eng.default_params(gapped=0))
+        assert eng.stats()['super_units'] == 2, tag   # the packed path: both strands of one super-scaffold, one batch
+    g.close()
+    assert outs['tiles'].size >= multi
+    assert outs['wave'].tobytes() == outs['tiles'].tobytes()
+    assert outs['two-level'].tobytes() == outs['tiles'].tobytes()
 
 
 def test_wave_and_two_level_kernels_agree_on_a_million_hsps(eng, monkeypatch):
