@@ -88,19 +88,11 @@ __device__ __forceinline__ void bound_block2(Bound2 &B, uint32_t v, uint32_t n, 
 
 // "a seed hit of this diagonal may start at frame bit B + i" for i = 0 .. 31 (bit i of the result), B = 13 + 32 k.
 // n0 / n1: the words of nm = dl | dh that hold bits B - 13 .. B + 50; d0 / d1: the same of dl.  CARE = the care
-// positions looked at (all twelve + TV: the exact 12of19 rule with one transition; fewer / no TV: a superset).
+// positions looked at (all twelve + TV: the exact 12of19 rule with one transition; fewer / no TV: a superset).  The count itself
+// is seed_window.h's carry-save network: 12 three-input functions per CARE10 word, 20 per CARE19 word with the transversion plane.
 template <uint32_t CARE, bool TV>
 __device__ __forceinline__ uint32_t seed_starts32(uint32_t n0, uint32_t n1, uint32_t d0, uint32_t d1, int transitions) {
-    uint32_t ones = 0, twos = 0, tv = 0;
-#pragma unroll
-    for (int c = 0; c < SEED_LEN; c++) {
-        if (!((CARE >> c) & 1u)) continue;
-        const uint32_t v = __builtin_amdgcn_alignbit(n1, n0, 13 + c);
-        twos |= ones & v;
-        ones |= v;
-        if (TV) tv |= __builtin_amdgcn_alignbit(d1, d0, 13 + c);
-    }
-    return ~(transitions ? (twos | tv) : ones);
+    return seed_window::starts32<SeedOps, CARE, TV, 13>(n0, n1, d0, d1, transitions);
 }
 
 // true = the pair is walked exactly.  Blocks of 24 columns (left: four, right: 24 + 24 + 16): seven blocks instead of

@@ -3,10 +3,18 @@
 // k4_extend.hip and by the fused seed-scan / extension kernel (k34_fused.hip).
 #pragma once
 #include "device_util.h"
+#include "seed_window.h"
 
 namespace mimeo {
 
 constexpr uint32_t CARE19 = 0x7A997u;  // care positions of 1110100110010101111 (bit i = offset i)
+// the device's primitives for seed_window.h (the care-position count of every filter here and in k34_fused.hip): one v_alignbit_b32,
+// one v_bitop3_b32 by truth table
+struct SeedOps {
+    static __device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
+    template <uint32_t TT>
+    static __device__ __forceinline__ uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, TT); }
+};
 constexpr int EXT_THREADS = 256;
 constexpr int LONG_WINDOWS = 8;  // per-lane walks give up after 8*32 bases per direction
 
@@ -317,17 +325,8 @@ __device__ __forceinline__ WinMasks left_masks(const Frame &F, uint32_t bt, int 
     const uint32_t cglo = __builtin_amdgcn_alignbit(F.cg[b + 1], F.cg[b], bt), cghi = __builtin_amdgcn_alignbit(F.cg[b + 2], F.cg[b + 1], bt);
     const uint32_t nnlo = __builtin_amdgcn_alignbit(F.nn[b + 1], F.nn[b], bt), nnhi = __builtin_amdgcn_alignbit(F.nn[b + 2], F.nn[b + 1], bt);
     const uint32_t nlo = dllo | dhlo, nhi = dlhi | dhhi;
-    uint32_t ones = 0, twos = 0, tv = 0;
-#pragma unroll
-    for (int c = 0; c < SEED_LEN; c++) {
-        if (!((CARE19 >> c) & 1u)) continue;
-        const uint32_t v = c ? __builtin_amdgcn_alignbit(nhi, nlo, c) : nlo;
-        twos |= ones & v;
-        ones |= v;
-        tv |= c ? __builtin_amdgcn_alignbit(dlhi, dllo, c) : dllo;
-    }
-    const uint32_t bad = transitions ? (twos | tv) : ones;
-    const uint32_t H = ~bad & __builtin_amdgcn_alignbit(F.st[b + 1], F.st[b], bt) & __builtin_amdgcn_alignbit(F.sq[b + 1], F.sq[b], bt);
+    const uint32_t H = seed_window::starts32<SeedOps, CARE19, true, 0>(nlo, nhi, dllo, dlhi, transitions) &
+                       __builtin_amdgcn_alignbit(F.st[b + 1], F.st[b], bt) & __builtin_amdgcn_alignbit(F.sq[b + 1], F.sq[b], bt);
     WinMasks m;
     m.dl = __brev(__builtin_amdgcn_alignbit(dlhi, dllo, SEED_LEN));
     m.dh = __brev(__builtin_amdgcn_alignbit(dhhi, dhlo, SEED_LEN));
@@ -438,17 +437,8 @@ __device__ __forceinline__ FilterMasks filter_left(const Frame &F, uint32_t bt, 
     const uint32_t dhlo = __builtin_amdgcn_alignbit(F.dh[b + 1], F.dh[b], bt), dhhi = __builtin_amdgcn_alignbit(F.dh[b + 2], F.dh[b + 1], bt);
     const uint32_t cglo = __builtin_amdgcn_alignbit(F.cg[b + 1], F.cg[b], bt), cghi = __builtin_amdgcn_alignbit(F.cg[b + 2], F.cg[b + 1], bt);
     const uint32_t nlo = dllo | dhlo, nhi = dlhi | dhhi;
-    uint32_t ones = 0, twos = 0, tv = 0;
-#pragma unroll
-    for (int c = 0; c < SEED_LEN; c++) {
-        if (!((CARE19 >> c) & 1u)) continue;
-        const uint32_t v = c ? __builtin_amdgcn_alignbit(nhi, nlo, c) : nlo;
-        twos |= ones & v;
-        ones |= v;
-        tv |= c ? __builtin_amdgcn_alignbit(dlhi, dllo, c) : dllo;
-    }
     FilterMasks m;
-    m.H = ~(transitions ? (twos | tv) : ones);
+    m.H = seed_window::starts32<SeedOps, CARE19, true, 0>(nlo, nhi, dllo, dlhi, transitions);
     m.dl = __builtin_amdgcn_alignbit(dlhi, dllo, SEED_LEN);
     m.dh = __builtin_amdgcn_alignbit(dhhi, dhlo, SEED_LEN);
     m.cg = __builtin_amdgcn_alignbit(cghi, cglo, SEED_LEN);
@@ -461,16 +451,7 @@ __device__ __forceinline__ FilterMasks filter_left(const Frame &F, uint32_t bt, 
         // which can only add alarms), and the eight care positions nearest the frame are tested
         const uint32_t dlm = __builtin_amdgcn_alignbit(F.dl[0], 0u, bt), dhm = __builtin_amdgcn_alignbit(F.dh[0], 0u, bt);
         const uint32_t nm = dlm | dhm;
-        uint32_t o2 = 0, w2 = 0, t2 = 0;
-#pragma unroll
-        for (int c = 0; c < SEED_LEN; c++) {
-            if (!((CARE8_HIGH >> c) & 1u)) continue;
-            const uint32_t v = __builtin_amdgcn_alignbit(nlo, nm, c);
-            w2 |= o2 & v;
-            o2 |= v;
-            t2 |= __builtin_amdgcn_alignbit(dllo, dlm, c);
-        }
-        m.H2 = ~(transitions ? (w2 | t2) : o2) & 0xFFFF0000u;  // window starts 16..1 bases in front of the low words
+        m.H2 = seed_window::starts32<SeedOps, CARE8_HIGH, true, 0>(nm, nlo, dlm, dllo, transitions) & 0xFFFF0000u;  // window starts 16..1 bases in front of the low words
     }
     return m;
 }

@@ -121,7 +121,9 @@ def main():
     while hi + 1 < len(per_block) and per_block[hi + 1]['depth'] >= d4:
         hi += 1
     rnd = per_block[lo:hi + 1]
-    filt = max(rnd, key=lambda b: b['bcnt'])
+    # (the first block with the seven blocks' popcounts behind the fetch: the flush filter further down the round loop holds
+    # more of them, and runs once per 64 STAGED pairs, not once per round)
+    filt = next(b for b in rnd[fetch - lo:] if b['bcnt'] >= 12)
     # the chunk visit: the depth-2/3 blocks around it (everything inside the segment loop that is not the round loop)
     seg_depth = d4 - 2
     vlo = lo
