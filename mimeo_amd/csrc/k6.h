@@ -209,7 +209,7 @@ struct K6Buffers {
 };
 extern K6Buffers g_k6;   // k6_gapped.hip
 // cap: the score beyond which 32-bit DP cells are rebased.  dp_round: k6_dp.hip; arena_reserve, trace_round: k6_trace.hip; paths_pass: k6_paths.hip
-int dp_round(Group *d_groups, uint32_t n, const mimeo_params *p, int32_t cap, bool bounded, const BoundCtx &bc, unsigned int *novf);
+int dp_round(Group *d_groups, uint32_t n, const mimeo_params *p, int32_t cap, bool bounded, const BoundCtx &bc, unsigned int *novf, unsigned int *nrestart);
 int arena_reserve(uint64_t blocks, uint64_t used);
 struct TraceStats { uint64_t arena_used, largest; float ms; uint32_t slices; };   // blocks in the arena, largest traceback of one half (bytes), kernel time, pool slices
 int trace_round(Group *d_groups, const DpJob *d_jobs, uint32_t h0, const mimeo_params *p, int32_t cap, uint64_t budget, TraceStats &ts, bool bounded, BoundCtx bc);

@@ -8,7 +8,7 @@ namespace mimeo {
 template <int WSTRIP>
 __device__ __forceinline__ void load_qbits(const GStrandView &Q, uint32_t aq, int dir, uint32_t jb, uint32_t lenB,
                                            uint32_t &qlo, uint32_t &qhi, uint32_t &qn) {
-    constexpr uint32_t SMASK = WSTRIP == 32 ? 0xFFFFFFFFu : ((1u << (WSTRIP & 31)) - 1u);  // WSTRIP in {14, 32}
+    constexpr uint32_t SMASK = WSTRIP == 32 ? 0xFFFFFFFFu : ((1u << (WSTRIP & 31)) - 1u);  // WSTRIP in {7, 14, 32}
     if (jb > lenB) { qlo = qhi = qn = 0; return; }
     if (dir > 0) {
         int32_t p = (int32_t)(aq + jb) - 1;
@@ -212,10 +212,29 @@ __device__ HalfResult wave_half_extend_2048(const GStrandView &T, const GStrandV
 // Measured: ~40 VALU instructions per cell.  Strips of 14 columns (896-column window): the widest live band of a
 // default-parameter extension is ~600 + 2 strips (y-drop 9400 / gap extend 30 on either side of the best cell; C4: all
 // below 768), and a band that does not fit is redone by the 2048-column kernel.
-constexpr int L_WS = 14, L_WINDOW = 64 * L_WS;
+// The strip width WS is a template parameter: a row costs about 36 * WS + 85 VALU instructions whatever part of its
+// 64 * WS columns is live, and the widest row of a half comes late: the deletion side of the band stays ~70 columns wide
+// while the best score keeps growing and reaches 300 only when the repeat ends.  So k6_dp1 starts a half at L_W1 = L_WS / 2
+// columns per lane (lean_dp<L_W1>, a 448-column window).  When a row ends with the last strip but one live, that row is
+// still complete: the wavefront lays its state out at L_WS (lean_widen) and goes on with the next row.  When the band
+// outgrows the narrow window in row 0, or reaches the last strip from further down in one row, the wavefront runs the half
+// again from row 1 at L_WS.  Only a half that outgrows L_WS is reported as an overflow.  Which lane holds a column
+// changes no cell, so the result does not depend on the width; and because a strip of L_W1 columns never straddles a
+// multiple of L_WS and the handover moves the window base down to one, the windows at L_WS, the overflow test and maxcols
+// are those of a pass that ran at L_WS from row 0.
+constexpr int L_WS = 14;   // the full width: k6_dp1_bounded, and k6_dp1 from the handover on
+constexpr int L_W1 = 7;    // k6_dp1's first rows
+static_assert(2 * L_W1 == L_WS, "lean_widen pairs up strips of L_W1 columns, and maxcols is counted in whole strips of L_WS");
+constexpr uint32_t LEAN_BAND = 1u, LEAN_ROWS = 2u, LEAN_WIDEN = 3u;   // why lean_dp left: the window (row 0 or a later row), the 16-bit counts, a handover
+struct ScoreTab { uint32_t t0, t1, t2, t3; };         // biased score bytes of the four query bases for each target base (index lo | hi << 1)
+template <int WS>
 struct LeanState {
-    int32_t C[L_WS], D[L_WS];
-    uint32_t Cc[L_WS], Dc[L_WS], sel[L_WS];
+    int32_t C[WS], D[WS];
+    uint32_t Cc[WS], Dc[WS], sel[WS];
+};
+struct LeanHandover {   // where a pass at half the width stood when its band reached the last strip but one: the rows done, the window base
+    HalfResult best;
+    uint32_t rows, wb;
 };
 // a cell of the lean kernel as it moves between lanes: score and packed counts (matches | diagonal steps << 16)
 struct PCell {
@@ -260,9 +279,10 @@ __device__ __forceinline__ PCell lean_incl_maxscan(PCell v) {
 }
 
 // byte selectors of a strip from its query bits: 0..3 = base code (lo | hi << 1), 4 = N; upper bytes select zero
-__device__ __forceinline__ void lean_selectors(LeanState &S, uint32_t qlo, uint32_t qhi, uint32_t qn) {
+template <int WS>
+__device__ __forceinline__ void lean_selectors(LeanState<WS> &S, uint32_t qlo, uint32_t qhi, uint32_t qn) {
 #pragma unroll
-    for (int s = 0; s < L_WS; s++) {
+    for (int s = 0; s < WS; s++) {
         const uint32_t idx = ((qlo >> s) & 1u) | (((qhi >> s) & 1u) << 1);
         S.sel[s] = 0x0C0C0C00u | (((qn >> s) & 1u) ? 4u : idx);
     }
@@ -271,15 +291,15 @@ __device__ __forceinline__ void lean_selectors(LeanState &S, uint32_t qlo, uint3
 // one DP row; returns the lane's row maximum (NEG when none of its cells is live).  BND (bounded extension, with EDGE):
 // exmask also clears the slots outside the row's allowed interval, and their H is dead before the insertion pass: the
 // forbidden cells are a prefix and a suffix of the row, so H masked after pass 1 and C / D after pass 3 is the rule
-template <bool EDGE, bool BND = false>
-__device__ __forceinline__ int32_t lean_row(LeanState &S, uint32_t srow, int32_t O, int32_t E, int32_t thr, uint32_t exmask,
+template <int WS, bool EDGE, bool BND = false>
+__device__ __forceinline__ int32_t lean_row(LeanState<WS> &S, uint32_t srow, int32_t O, int32_t E, int32_t thr, uint32_t exmask,
                                             int32_t lane_base, int32_t kneg128) {
     const int32_t OE = O + E;
     // C of the column left of my strip (previous row): last slot of the previous lane
-    PCell pc = dpp_pcell<0x138, 0xf>(PCell{S.C[L_WS - 1], S.Cc[L_WS - 1]});
+    PCell pc = dpp_pcell<0x138, 0xf>(PCell{S.C[WS - 1], S.Cc[WS - 1]});
     // pass 1 (slots descending, in place): D and H = max(diagonal, D); slot s still sees the old C of slot s - 1
 #pragma unroll
-    for (int s = L_WS - 1; s >= 0; s--) {
+    for (int s = WS - 1; s >= 0; s--) {
         const int32_t t1 = S.D[s] - E, t2 = S.C[s] - OE;
         const bool open = t2 > t1;
         const int32_t ds = max(t1, t2);
@@ -297,18 +317,18 @@ __device__ __forceinline__ int32_t lean_row(LeanState &S, uint32_t srow, int32_t
     // pass 2: the strip's aggregate of the insertion state as it arrives at the first column of the next strip
     PCell run{NEG, 0};
 #pragma unroll
-    for (int s = 0; s < L_WS; s++) {
+    for (int s = 0; s < WS; s++) {
         const bool take = S.C[s] > run.s;  // ties -> left
         run.c = take ? S.Cc[s] : run.c;
         run.s = max(run.s, S.C[s]) - E;
     }
     run.s += lane_base;  // common frame: column 0 of the window
     PCell acc = dpp_pcell<0x138, 0xf>(lean_incl_maxscan(run));  // best of every column left of my strip
-    acc.s += L_WS * E - lane_base;                                   // ... as it arrives at my first column
+    acc.s += WS * E - lane_base;                                   // ... as it arrives at my first column
     // pass 3: C = max(H, I), prune, row maximum
     int32_t rowmax = NEG;
 #pragma unroll
-    for (int s = 0; s < L_WS; s++) {
+    for (int s = 0; s < WS; s++) {
         const int32_t hs = S.C[s];
         const uint32_t hc = S.Cc[s];
         const int32_t is = acc.s - O;
@@ -327,63 +347,64 @@ __device__ __forceinline__ int32_t lean_row(LeanState &S, uint32_t srow, int32_t
     return rowmax;
 }
 
-// BOUND: the extension is bounded by the group's nacc accepted alignments (bounds_at); *sw receives what it swept
-template <bool BOUND>
-__device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir,
-                                            int32_t O, int32_t E, int32_t Y, const BoundCtx &B, uint64_t b0, uint32_t nacc,
-                                            HalfSweep *sw) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t lenA = dir > 0 ? T.len - at : at, lenB = dir > 0 ? Q.len - aq : aq;
-    HalfResult best{0, 0, 0, 0, 0, 0, 0, 0};
-    if (BOUND) *sw = HalfSweep{0, 0, nacc, 0};
-    // a bounded half may take the exact shortcut only when no earlier alignment reaches into its rows
-    if ((!BOUND || bounds_none(B, b0, nacc, at, dir)) && identical_suffix(T, Q, at, aq, dir, best)) return best;
-    // biased score bytes of the four query bases for each target base (index lo | hi << 1)
-    uint32_t tab[4];
-#pragma unroll
-    for (uint32_t a = 0; a < 4; a++) {
-        uint32_t w = 0;
-#pragma unroll
-        for (uint32_t b = 0; b < 4; b++) {
-            const uint32_t alo = a & 1u, ahi = a >> 1, dl = alo ^ (b & 1u), dh = ahi ^ (b >> 1);
-            w |= (uint32_t)(sub_score(dl, dh, alo ^ ahi, 0u) + 128) << (8u * b);
-        }
-        tab[a] = w;
-    }
-    LeanState S;
-    uint32_t wb = 0, jb = lane * L_WS;
-    {
-        uint32_t qlo, qhi, qn;
-        load_qbits<L_WS>(Q, aq, dir, jb, lenB, qlo, qhi, qn);
-        lean_selectors(S, qlo, qhi, qn);
-    }
+// row 0 of a half in a fresh window at column 0: C(0, j) = -O - j E while that stays within the y-drop; false when it does not fit
+template <int WS>
+__device__ __forceinline__ bool lean_row0(const GStrandView &Q, uint32_t aq, int dir, uint32_t lenB, int32_t O, int32_t E, int32_t Y,
+                                          LeanState<WS> &S) {
+    const uint32_t jb = (threadIdx.x & 63u) * WS;
+    uint32_t qlo, qhi, qn;
+    load_qbits<WS>(Q, aq, dir, jb, lenB, qlo, qhi, qn);
+    lean_selectors<WS>(S, qlo, qhi, qn);
     bool over = false;
 #pragma unroll
-    for (int s = 0; s < L_WS; s++) {
+    for (int s = 0; s < WS; s++) {
         const uint32_t j = jb + s;
         const int32_t v = j ? -O - (int32_t)j * E : 0;
         const bool alive = j <= lenB && (j == 0 || v >= -Y);
         S.C[s] = alive ? v : NEG; S.Cc[s] = 0;
         S.D[s] = NEG; S.Dc[s] = 0;
-        if (alive && j >= (uint32_t)(L_WINDOW - L_WS)) over = true;
+        if (alive && j >= (uint32_t)(64 * WS - WS)) over = true;
     }
-    if (__ballot(over)) { best.overflow = 1; return best; }
-    const int32_t lane_base = (int32_t)(lane * L_WS) * E;
+    return __ballot(over) == 0;
+}
+
+// The row loop of the lean kernel at WS columns per lane.  S holds row ho.rows of the half in the window at column ho.wb, ho.best what
+// the rows so far came to (row 0: lean_row0 and a zeroed ho).  The result's overflow says why the pass left before the half was
+// done (LEAN_BAND, LEAN_ROWS; LEAN_WIDEN: ho then says where it stands), 0 when it is done.  BOUND (WS == L_WS only): the
+// extension is bounded by the group's nacc accepted alignments (bounds_at); *sw receives what it swept.
+// maxcols is always the figure of the L_WS layout, 14 * (max over rows of hi_i / 14 - lo_{i-1} / 14 + 1) with the first / last live
+// column of a row: the window base and the last live strip give those two quotients at either width.
+template <int WS, bool BOUND>
+__device__ __forceinline__ HalfResult lean_dp(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir, int32_t O,
+                                              int32_t E, int32_t Y, const ScoreTab tab, const BoundCtx &B, uint64_t b0, uint32_t nacc,
+                                              HalfSweep *sw, LeanState<WS> &S, LeanHandover &ho) {
+    static_assert(!BOUND || WS == L_WS, "the bounded kernel runs at the full width");
+    constexpr int WINDOW = 64 * WS;
+    constexpr bool WIDENS = WS == L_W1;   // the pass hands over to L_WS instead of giving up
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lenA = dir > 0 ? T.len - at : at, lenB = dir > 0 ? Q.len - aq : aq;
+    HalfResult best = ho.best;
+    best.overflow = 0;
+    uint32_t wb = ho.wb, jb = wb + lane * WS;
+    const uint32_t i0 = ho.rows + 1u;
+    const int32_t lane_base = (int32_t)(lane * WS) * E;
     const int32_t kneg128 = __builtin_amdgcn_readfirstlane(-128);
-    uint32_t exmask = (1u << L_WS) - 1u;
-    bool edge = wb + (uint32_t)L_WINDOW - 1u > lenB;
+    uint32_t exmask = (1u << WS) - 1u;
+    bool edge = wb + (uint32_t)WINDOW - 1u > lenB;
     if (edge) {
         exmask = 0;
 #pragma unroll
-        for (int s = 0; s < L_WS; s++) exmask |= (jb + s <= lenB ? 1u : 0u) << s;
+        for (int s = 0; s < WS; s++) exmask |= (jb + s <= lenB ? 1u : 0u) << s;
     }
     long long bkmin = -K_INF, bkmax = K_INF;   // BOUND: the allowed interval of k = j - i, and the row where it is looked up again
     uint32_t bnext = 1u;
     int32_t klo = INT32_MAX, khi = INT32_MIN;
-    RowBases rbase{0, 0, 0}, rnext = load_row_bases(T, at, dir, 1u);
-    for (uint32_t i = 1; i <= lenA; i++) {
+    const uint32_t blk = ((i0 - 1u) & ~31u) + 1u;   // first row of the block of 32 target bases that holds row i0
+    RowBases rbase{0, 0, 0}, rnext = load_row_bases(T, at, dir, blk);
+    if ((i0 - 1u) & 31u) { rbase = rnext; rnext = load_row_bases(T, at, dir, blk + 32u); }
+    for (uint32_t i = i0; i <= lenA; i++) {
         // the packed counts hold 16 bits each: a longer extension is redone by the wide kernel (unpacked counts)
-        if (i >= 0xFFFFu) { best.overflow = 1; break; }
+        if (i >= 0xFFFFu) { best.overflow = LEAN_ROWS; break; }
         if (BOUND && i == bnext) {
             const RowBound rb = bounds_at(B, b0, nacc, at, aq, dir, i);
             bkmin = rb.kmin; bkmax = rb.kmax; bnext = rb.next;
@@ -394,7 +415,7 @@ __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandV
         const uint32_t rlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)rbase.lo), rhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)rbase.hi),
                        rnm = (uint32_t)__builtin_amdgcn_readfirstlane((int)rbase.nm);
         const uint32_t a = ((rlo >> rbit) & 1u) | (((rhi >> rbit) & 1u) << 1);
-        uint32_t srow = a & 2u ? (a & 1u ? tab[3] : tab[2]) : (a & 1u ? tab[1] : tab[0]);
+        uint32_t srow = a & 2u ? (a & 1u ? tab.t3 : tab.t2) : (a & 1u ? tab.t1 : tab.t0);
         if ((rnm >> rbit) & 1u) srow = 0x1C1C1C1Cu;
         // BOUND: the allowed columns of this row are jlo .. jhi; only rows in which they cut the window run the masked variant
         uint32_t bm = 0;
@@ -402,23 +423,27 @@ __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandV
         if (BOUND) {
             const long long jlo = bkmin + (long long)i + 1, jhi = bkmax + (long long)i - 1;
             if (bkmin > -K_INF || bkmax < K_INF) sw->nbound++;
-            cut = jlo > (long long)wb || jhi < (long long)wb + (L_WINDOW - 1);
+            cut = jlo > (long long)wb || jhi < (long long)wb + (WINDOW - 1);
             const long long r0 = jlo - (long long)jb, r1 = jhi - (long long)jb + 1;
-            const uint32_t s0 = (uint32_t)min(max(r0, 0ll), (long long)L_WS), s1 = (uint32_t)min(max(r1, 0ll), (long long)L_WS);
+            const uint32_t s0 = (uint32_t)min(max(r0, 0ll), (long long)WS), s1 = (uint32_t)min(max(r1, 0ll), (long long)WS);
             bm = ((1u << s1) - 1u) & ~((1u << s0) - 1u) & exmask;   // exmask: all slots, or those within the query
         }
-        const int32_t rowmax = BOUND && cut ? lean_row<true, true>(S, srow, O, E, thr, bm, lane_base, kneg128)
-                               : edge ? lean_row<true>(S, srow, O, E, thr, exmask, lane_base, kneg128)
-                                      : lean_row<false>(S, srow, O, E, thr, exmask, lane_base, kneg128);
+        const int32_t rowmax = BOUND && cut ? lean_row<WS, true, true>(S, srow, O, E, thr, bm, lane_base, kneg128)
+                               : edge ? lean_row<WS, true>(S, srow, O, E, thr, exmask, lane_base, kneg128)
+                                      : lean_row<WS, false>(S, srow, O, E, thr, exmask, lane_base, kneg128);
         const uint64_t ball = __ballot(rowmax > NEGH);
         if (!ball) break;
         const uint32_t rf = (uint32_t)__builtin_ctzll(ball), rl = 63u - (uint32_t)__builtin_clzll(ball);
-        if (rl == 63u) { best.overflow = 1; break; }
-        best.maxcols = max(best.maxcols, (rl + 1u) * L_WS);
+        if (rl == 63u) { best.overflow = LEAN_BAND; break; }
+        if constexpr (WS == L_WS) {
+            best.maxcols = max(best.maxcols, (rl + 1u) * WS);
+        } else {   // no strip straddles a multiple of L_WS
+            best.maxcols = max(best.maxcols, ((wb + rl * WS) / L_WS + 1u - wb / L_WS) * L_WS);
+        }
         best.rows = i;
         if (BOUND) {   // the strips with a live cell, as diagonals of this row
-            klo = min(klo, (int32_t)((long long)wb + rf * L_WS - (long long)i));
-            khi = max(khi, (int32_t)((long long)wb + (rl + 1u) * L_WS - 1 - (long long)i));
+            klo = min(klo, (int32_t)((long long)wb + rf * WS - (long long)i));
+            khi = max(khi, (int32_t)((long long)wb + (rl + 1u) * WS - 1 - (long long)i));
         }
         const int32_t wmax = wave_max_i32(rowmax);
         if (wmax > best.score) {
@@ -426,20 +451,20 @@ __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandV
             const uint32_t L = (uint32_t)__builtin_ctzll(__ballot(rowmax == wmax));
             uint32_t slot = 0, cnt = 0;
 #pragma unroll
-            for (int s = L_WS - 1; s >= 0; s--) {
+            for (int s = WS - 1; s >= 0; s--) {
                 const int32_t v = __builtin_amdgcn_readlane(S.C[s], (int)L);
                 if (v == wmax) { slot = (uint32_t)s; cnt = (uint32_t)__builtin_amdgcn_readlane((int)S.Cc[s], (int)L); }
             }
-            best.score = wmax; best.i = i; best.j = wb + L * L_WS + slot; best.nm = cnt & 0xFFFFu; best.nx = (cnt >> 16) - (cnt & 0xFFFFu);
+            best.score = wmax; best.i = i; best.j = wb + L * WS + slot; best.nm = cnt & 0xFFFFu; best.nx = (cnt >> 16) - (cnt & 0xFFFFu);
         }
         // slide the window so that it starts at the strip holding the first live column
         if (rf) {
-            wb += rf * L_WS;
-            jb = wb + lane * L_WS;
+            wb += rf * WS;
+            jb = wb + lane * WS;
             const int src = (int)((lane + rf) & 63u);
             const bool fresh = lane + rf >= 64u;  // strip re-enters on the right with new columns
 #pragma unroll
-            for (int s = 0; s < L_WS; s++) {
+            for (int s = 0; s < WS; s++) {
                 const int32_t cs = __shfl(S.C[s], src), ds = __shfl(S.D[s], src);
                 S.Cc[s] = __shfl(S.Cc[s], src); S.Dc[s] = __shfl(S.Dc[s], src);
                 S.sel[s] = __shfl(S.sel[s], src);
@@ -448,27 +473,108 @@ __device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandV
             }
             if (fresh) {
                 uint32_t qlo, qhi, qn;
-                load_qbits<L_WS>(Q, aq, dir, jb, lenB, qlo, qhi, qn);
-                lean_selectors(S, qlo, qhi, qn);
+                load_qbits<WS>(Q, aq, dir, jb, lenB, qlo, qhi, qn);
+                lean_selectors<WS>(S, qlo, qhi, qn);
             }
-            edge = wb + (uint32_t)L_WINDOW - 1u > lenB;
+            edge = wb + (uint32_t)WINDOW - 1u > lenB;
             if (edge) {
                 exmask = 0;
 #pragma unroll
-                for (int s = 0; s < L_WS; s++) exmask |= (jb + s <= lenB ? 1u : 0u) << s;
-            } else if (BOUND) exmask = (1u << L_WS) - 1u;
+                for (int s = 0; s < WS; s++) exmask |= (jb + s <= lenB ? 1u : 0u) << s;
+            } else if (BOUND) exmask = (1u << WS) - 1u;
         }
+        // the last strip but one is live and the last one dead: the row is complete, the next one may not be.  Hand over
+        if (WIDENS && rl == 62u) { best.overflow = LEAN_WIDEN; ho.best = best; ho.rows = i; ho.wb = wb; break; }
     }
     if (BOUND) { sw->klo = klo; sw->khi = khi; }
     return best;
 }
 
+// the state of a pass at L_W1 = L_WS / 2 columns per lane in the window at wb, laid out at L_WS: the window base moves down to a multiple
+// of L_WS (so the pass that goes on has the windows of a pass that started at L_WS), new lane L takes the old lanes 2L - odd and
+// 2L + 1 - odd, and what lies outside the old window enters dead, as strips that slide in on the right do
+__device__ __forceinline__ void lean_widen(const LeanState<L_W1> &N, LeanState<L_WS> &S, uint32_t &wb, const GStrandView &Q, uint32_t aq,
+                                           int dir, uint32_t lenB) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int odd = (int)((wb / L_W1) & 1u);
+    wb -= (uint32_t)odd * L_W1;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const int src = 2 * (int)lane + h - odd;
+        const bool dead = src < 0 || src > 63;
+#pragma unroll
+        for (int s = 0; s < L_W1; s++) {
+            const int32_t cs = __shfl(N.C[s], src & 63), ds = __shfl(N.D[s], src & 63);
+            S.Cc[h * L_W1 + s] = __shfl(N.Cc[s], src & 63); S.Dc[h * L_W1 + s] = __shfl(N.Dc[s], src & 63);
+            S.C[h * L_W1 + s] = dead ? NEG : cs;
+            S.D[h * L_W1 + s] = dead ? NEG : ds;
+        }
+    }
+    uint32_t qlo, qhi, qn;
+    load_qbits<L_WS>(Q, aq, dir, wb + lane * L_WS, lenB, qlo, qhi, qn);
+    lean_selectors<L_WS>(S, qlo, qhi, qn);
+}
+
+// A half extension by one wavefront: the shortcut, else lean_dp.  Unbounded: at L_W1 first; a pass at half the width hands over to
+// L_WS when its band reaches the last strip but one (*event = LEAN_WIDEN), and a half whose band outgrew the first window in row 0
+// or in one row runs again from row 1 at L_WS (*event = LEAN_BAND).  The result's overflow is 1 when the half needs the next kernel.
+template <bool BOUND>
+__device__ HalfResult wave_half_extend_lean(const GStrandView &T, const GStrandView &Q, uint32_t at, uint32_t aq, int dir,
+                                            int32_t O, int32_t E, int32_t Y, const BoundCtx &B, uint64_t b0, uint32_t nacc,
+                                            HalfSweep *sw, uint32_t *event) {
+    HalfResult best{0, 0, 0, 0, 0, 0, 0, 0};
+    if (BOUND) *sw = HalfSweep{0, 0, nacc, 0};
+    // a bounded half may take the exact shortcut only when no earlier alignment reaches into its rows
+    if ((!BOUND || bounds_none(B, b0, nacc, at, dir)) && identical_suffix(T, Q, at, aq, dir, best)) return best;
+    uint32_t t[4];
+#pragma unroll
+    for (uint32_t a = 0; a < 4; a++) {
+        uint32_t w = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 4; b++) {
+            const uint32_t alo = a & 1u, ahi = a >> 1, dl = alo ^ (b & 1u), dh = ahi ^ (b >> 1);
+            w |= (uint32_t)(sub_score(dl, dh, alo ^ ahi, 0u) + 128) << (8u * b);
+        }
+        t[a] = w;
+    }
+    const ScoreTab tab{t[0], t[1], t[2], t[3]};
+    const uint32_t lenB = dir > 0 ? Q.len - aq : aq;
+    LeanState<L_WS> S;
+    LeanHandover ho{best, 0u, 0u};
+    bool full0 = true;   // the full-width pass starts at row 0
+    if constexpr (!BOUND) {
+        LeanState<L_W1> N;
+        if (lean_row0<L_W1>(Q, aq, dir, lenB, O, E, Y, N)) {
+            best = lean_dp<L_W1, false>(T, Q, at, aq, dir, O, E, Y, tab, B, b0, nacc, sw, N, ho);
+            if (best.overflow == 0u || best.overflow == LEAN_ROWS) { best.overflow = best.overflow ? 1u : 0u; return best; }
+        } else best.overflow = LEAN_BAND;
+        if (best.overflow == LEAN_WIDEN) {
+            lean_widen(N, S, ho.wb, Q, aq, dir, lenB);
+            full0 = false;
+            *event = LEAN_WIDEN;
+        } else {
+            ho = LeanHandover{HalfResult{0, 0, 0, 0, 0, 0, 0, 0}, 0u, 0u};
+            *event = LEAN_BAND;
+        }
+    }
+    if (full0 && !lean_row0<L_WS>(Q, aq, dir, lenB, O, E, Y, S)) { best = HalfResult{0, 0, 0, 0, 0, 0, 0, 0}; best.overflow = 1u; return best; }
+    best = lean_dp<L_WS, BOUND>(T, Q, at, aq, dir, O, E, Y, tab, B, b0, nacc, sw, S, ho);
+    best.overflow = best.overflow ? 1u : 0u;
+    return best;
+}
+
+// nrestart[0] counts the halves that ran a second time at the full width, nrestart[1] those that went on at it (MIMEO_K6_STATS)
 __global__ __launch_bounds__(64) void k6_dp1(const Group *__restrict__ groups, const DpJob *__restrict__ jobs,
-                                             HalfResult *__restrict__ res, int32_t O, int32_t E, int32_t Y) {
+                                             HalfResult *__restrict__ res, int32_t O, int32_t E, int32_t Y,
+                                             unsigned int *__restrict__ nrestart) {
     const DpJob job = jobs[blockIdx.x];
     const Group &G = groups[job.group];
-    HalfResult r = wave_half_extend_lean<false>(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, BoundCtx{}, 0, 0, nullptr);
-    if (threadIdx.x == 0) res[job.slot] = r;
+    uint32_t event = 0;
+    HalfResult r = wave_half_extend_lean<false>(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, BoundCtx{}, 0, 0, nullptr, &event);
+    if (threadIdx.x == 0) {
+        res[job.slot] = r;
+        if (event) atomicAdd(nrestart + (event == LEAN_WIDEN ? 1 : 0), 1u);
+    }
 }
 
 // k6_dp1 under mimeo_params.bound_extensions.  A half that does not fit (band, rows) goes on to k6_dp_any<true>
@@ -479,7 +585,7 @@ __global__ __launch_bounds__(64) void k6_dp1_bounded(const Group *__restrict__ g
     const DpJob job = jobs[blockIdx.x];
     const Group &G = groups[job.group];
     HalfSweep sw;
-    HalfResult r = wave_half_extend_lean<true>(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, B, G.hsp_begin, G.nacc, &sw);
+    HalfResult r = wave_half_extend_lean<true>(G.T, G.Q, job.at, job.aq, job.dir, O, E, Y, B, G.hsp_begin, G.nacc, &sw, nullptr);
     if (threadIdx.x == 0) {
         res[job.slot] = r;
         sweep[job.slot] = sw;
@@ -576,7 +682,7 @@ __global__ void k6_list_all(uint32_t n, unsigned int *__restrict__ novf, unsigne
 // 2048-column kernel (not in bounded mode: it knows no bounds), the global-memory kernel.  The lean kernel's dead-cell
 // arithmetic needs the penalties to stay far below 2^29 / 1024; beyond that every job starts at the second kernel of its mode.
 int dp_round(Group *d_groups, uint32_t n, const mimeo_params *p, int32_t cap, bool bounded, const BoundCtx &bc,
-                    unsigned int *novf) {
+                    unsigned int *novf, unsigned int *nrestart) {
     hipStream_t st = stream();
     int rc;
     const Group *groups = d_groups;
@@ -590,7 +696,7 @@ int dp_round(Group *d_groups, uint32_t n, const mimeo_params *p, int32_t cap, bo
         if (lean_ok) hipLaunchKernelGGL(k6_dp1_bounded, dim3(n), dim3(64), 0, st, groups, jobs, res, sweep, O, E, Y, bc, novf, list);
         else hipLaunchKernelGGL(k6_list_all, dim3((n + 255) / 256), dim3(256), 0, st, n, novf, list);
     } else {
-        if (lean_ok) hipLaunchKernelGGL(k6_dp1, dim3(n), dim3(64), 0, st, groups, jobs, res, O, E, Y);
+        if (lean_ok) hipLaunchKernelGGL(k6_dp1, dim3(n), dim3(64), 0, st, groups, jobs, res, O, E, Y, nrestart);
         hipLaunchKernelGGL(k6_dp_wide, dim3(n), dim3(64), 0, st, groups, jobs, res, O, E, Y, novf, list, cap, lean_ok ? 0 : 1);
     }
     // bands beyond 2048 columns (tandem arrays): the global-memory kernel, a few jobs at a time

@@ -12,7 +12,8 @@
 //     Three kernels (k6_dp.hip), each taking the jobs the one before could not hold (dp_round):
 //       - k6_dp1, the lean kernel: one wavefront, lane l owns the 14-column strip (j / 14) % 64 == l
 //         of an 896-column window that slides with the first live column, all state in registers,
-//         counts packed into 16 bits each (65 535 rows at most);
+//         counts packed into 16 bits each (65 535 rows at most); a half starts at 7-column strips (448
+//         columns) and moves to 14 when its band reaches the last strip but one (k6_dp.hip);
 //       - k6_dp_wide, the second chance: the same layout with 32-column strips (2048 columns),
 //         unpacked counts and no row limit;
 //       - k6_dp_any, the last resort: one workgroup, the rows in global memory, bands up to 2^16
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(256) void k6_ungapped_paths(const Group *__restrict
 K6Buffers g_k6;
 
 // MIMEO_K6_STATS: what the DP kernels made of the round's n jobs, on stderr; bounded mode: *bound_jobs counts those that met a bound
-static int round_stats(uint32_t n, uint64_t nhsps, bool bounded, unsigned long long *bound_jobs) {
+static int round_stats(uint32_t n, uint64_t nhsps, bool bounded, unsigned long long *bound_jobs, const unsigned int *nrestart) {
     std::vector<DpJob> hj(n);
     std::vector<HalfResult> hall((size_t)nhsps * 2), hr(n);
     HIP_TRY(hipStreamSynchronize(stream()));
@@ -454,6 +455,9 @@ static int round_stats(uint32_t n, uint64_t nhsps, bool bounded, unsigned long l
     }
     unsigned long long rebased = 0;
     for (auto &r : hr) if (r.base_lo | r.base_hi) rebased++;
+    unsigned int wide[2] = {0, 0};   // k6_dp1: halves whose band outgrew the first, narrower window: run again at the full width, gone on at it
+    HIP_TRY(hipMemcpy(wide, nrestart, 8, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[k6] full strip width: restarted %u widened %u of %u\n", wide[0], wide[1], n);
     fprintf(stderr, "[k6] jobs %u shortcut %llu (rebased in k6_dp_any: %llu) rows total %llu max %llu band<128..>=1024:", n, shortcut, rebased, rows, maxr);
     for (int b = 0; b < 9; b++) fprintf(stderr, " %llu", hist[b]);
     fprintf(stderr, "\n");
@@ -507,7 +511,7 @@ static int gapped_setup(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_so
     if ((rc = g_k6.res.reserve((size_t)nhsps * 2 * sizeof(HalfResult)))) return rc;
     if ((rc = g_k6.astate.reserve((size_t)nhsps * 2))) return rc;  // state | defer count
     HIP_TRY(hipMemsetAsync(g_k6.astate.p, 0, (size_t)nhsps * 2, st));
-    if ((rc = g_k6.cnt.reserve(16))) return rc;
+    if ((rc = g_k6.cnt.reserve(32))) return rc;
     if ((rc = g_k6.ovf_list.reserve((size_t)ngroups * c.bmax * 2 * sizeof(unsigned int)))) return rc;
     // many small groups (scaffold pairs of a packed fragmented assembly): one workgroup each will do
     const uint32_t asplit = ngroups > 4096 ? 1u : ANCHOR_SPLIT;
@@ -541,8 +545,8 @@ static int gapped_rounds(Group *d_groups, uint32_t ngroups, uint64_t nhsps, cons
                          : c.box_paths ? k6_resolve<false, false, true> : k6_resolve<false, false>;
     const HalfSweep *sweep = c.bounded ? (const HalfSweep *)g_k6.sweep.p : nullptr;
     for (;;) {
-        HIP_TRY(hipMemsetAsync(g_k6.cnt.p, 0, 16, st));
-        unsigned int *njobs = (unsigned int *)g_k6.cnt.p, *remaining = njobs + 1, *novf = njobs + 2;
+        HIP_TRY(hipMemsetAsync(g_k6.cnt.p, 0, 32, st));
+        unsigned int *njobs = (unsigned int *)g_k6.cnt.p, *remaining = njobs + 1, *novf = njobs + 2, *nrestart = njobs + 4;
         pv.blk = (const PathBlock *)g_k6.arena.p;   // the arena may have grown in the last round
         hipLaunchKernelGGL(pick, dim3(ngroups), dim3(64), 0, st, d_groups, (const uint2 *)g_k6.anchors.p, (const mimeo_alignment *)d_aln,
                            c.bmax, (uint8_t *)g_k6.astate.p, (uint8_t *)g_k6.astate.p + nhsps, (DpJob *)g_k6.jobs.p, njobs, pv);
@@ -551,8 +555,8 @@ static int gapped_rounds(Group *d_groups, uint32_t ngroups, uint64_t nhsps, cons
         HIP_TRY(hipStreamSynchronize(st));
         if (h0) {
             const BoundCtx bc{(const mimeo_alignment *)d_aln, (const uint2 *)g_k6.anchors.p, pv};
-            if ((rc = dp_round(d_groups, h0, p, c.cap, c.bounded, bc, novf))) return rc;
-            if (c.stats && (rc = round_stats(h0, nhsps, c.bounded, &c.bound_jobs))) return rc;
+            if ((rc = dp_round(d_groups, h0, p, c.cap, c.bounded, bc, novf, nrestart))) return rc;
+            if (c.stats && (rc = round_stats(h0, nhsps, c.bounded, &c.bound_jobs, nrestart))) return rc;
             if (c.path) {
                 c.rounds++;
                 if ((rc = trace_round(d_groups, (const DpJob *)g_k6.jobs.p, h0, p, c.cap, c.pool_budget, c.ts, c.bounded, bc))) return rc;
