@@ -202,6 +202,7 @@ struct ExtStats {
 // follower_key_bits().  ExtBatch feeds it counters and free memory and makes the HIP calls.
 struct ExtQueues;     // k4_device.h
 struct ExtCounters;
+struct K34Buffers;    // k34.h
 // development / test switches of a batch, read from the environment once per batch (k4_extend.hip: read_switches): MIMEO_HEAVY=v1,
 // MIMEO_K4_STATS, MIMEO_TRACE, MIMEO_K4_VARIANT, MIMEO_K34_DEBUG, MIMEO_QUEUE_SHRINK (smaller queues; tests: force the rerun),
 // MIMEO_QUEUE_BUDGET_MB (tests: force the split)
@@ -213,9 +214,9 @@ struct ExtSwitches {
     long budget_mb = 0;
 };
 struct ExtBatch {
-    // mirror: mirror_dst_ on the device + one counter; plan_buf: the split pass's plan (k34_plan); funits: per-unit table of the heavy
-    // kernels (FusedUnit); nwalk_u: walk-queue counters per unit and shard + split-pass tile counts
-    DeviceBuf units, ctr, nsel, unit_hits, tile_hits, selfs, hits, bigcand, bigacc, heavy, mirror, plan_buf, funits, nwalk_u;
+    // mirror: mirror_dst_ on the device + one counter; funits: per-unit table of the heavy kernels (FusedUnit)
+    DeviceBuf units, ctr, nsel, unit_hits, tile_hits, selfs, hits, bigcand, bigacc, mirror, funits;
+    K34Buffers *k34_ = nullptr;   // K34's own buffers (k34.h: tile lists, split-pass plan, per-unit counters), owned
     // hipMalloc / hipFree of tens of GB cost seconds (C5 at full size spent 80 % of its wall time there): the queues of a batch are
     // slices of ONE allocation that only ever grows (arena_q, carved per batch: qbuf), the follower sort's buffers of another
     // (arena_s: sbuf).  The 8 GiB and 4 GiB of head-room they leave when they grow differ on purpose: the queue arena is allocated
@@ -257,7 +258,6 @@ struct ExtBatch {
     std::vector<uint64_t> walk_cap_u_;   // walk-queue capacity per unit and shard
     uint64_t walk_entries_ = 0;          // ... all regions together
     uint32_t nactive_ = 0;               // units of the batch that launch the heavy kernels
-    const unsigned int *plan_ctr_ = nullptr;   // the split pass plan's counters on the device (statistics)
     double expect_hits_ = 0;
     queue_plan::KeyBits key_ = {0, 0, 0, false};
     bool started_ = false, splittable_ = false;

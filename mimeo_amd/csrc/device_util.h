@@ -65,6 +65,18 @@ __device__ __forceinline__ uint32_t pext12(uint32_t x) {
            ((x >> 7) & 0xF00u);
 }
 
+// inclusive prefix sum of c over the 64 lanes of a wavefront: DPP (VALU latency), not six trips through the LDS crossbar
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t c) {
+    uint32_t inc = c;
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, false);   // row_shr:1
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, false);   // row_shr:2
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, false);   // row_shr:4
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, false);   // row_shr:8
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xa, 0xf, false);   // row_bcast:15
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x143, 0xc, 0xf, false);   // row_bcast:31
+    return inc;
+}
+
 struct Win32 { uint32_t lo, hi, nm, sv; };
 struct Win64 { uint64_t lo, hi, nm, sv; };
 

@@ -1,6 +1,6 @@
 // k4_device.h — device-side building blocks of the gap-free extension (K4): the exact x-drop walks, the pre-filter
 // bounds, the wavefront-cooperative long walks and the record emitters.  Shared by the tail kernels of
-// k4_extend.hip and by the fused seed-scan / extension kernel (k34_fused.hip).
+// k4_extend.hip and by the fused seed-scan / extension kernel (k34_fused.hip, k34_filter.h).
 #pragma once
 #include "device_util.h"
 #include "seed_window.h"
@@ -8,7 +8,7 @@
 namespace mimeo {
 
 constexpr uint32_t CARE19 = 0x7A997u;  // care positions of 1110100110010101111 (bit i = offset i)
-// the device's primitives for seed_window.h (the care-position count of every filter here and in k34_fused.hip): one v_alignbit_b32,
+// the device's primitives for seed_window.h (the care-position count of every filter here and in k34_filter.h): one v_alignbit_b32,
 // one v_bitop3_b32 by truth table
 struct SeedOps {
     static __device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
@@ -31,16 +31,8 @@ struct ExtCounters {
     unsigned long long nbigcand;   // candidates longer than ENT_LONG columns: their entropy is counted by the whole grid
     unsigned long long long_next, seg_next;  // k4_extend_long / k4_resolve_segments: next long hit / large segment to hand out
     unsigned long long nwalk_total, nwalk_over;  // walk-queue entries of the batch; fullest shard of any unit, in 1/1024 of its capacity (> 1024: overflow)
-    unsigned long long dbg[8];  // development (MIMEO_K34_DEBUG & 8): why the pre-filter passed a hit on
 };
 
-struct HeavyPlan {                       // the listed tiles of the whole batch, dense (k34_plan)
-    const unsigned long long *est;       // per listed slot (unit * NTILE + i): the first pass's estimate of the tile's hits
-    uint2 *tile;                         // dense k -> (unit index in the launch, tile)
-    uint32_t *base;                      // dense k -> first part; base[ntiles] = all parts
-    uint4 *split;                        // dense k -> (target shares, query ranges, entries per query range, 0)
-    unsigned int *ctr;                   // [0] parts handed out, [1] listed tiles, [2] parts
-};
 struct Cand {
     uint32_t tstart, qstart, len;
     int32_t raw;  // RAW_SATURATED: the score does not fit (a gap-free segment beyond ~21 Mbp); k4_entropy recounts it in 64 bits
@@ -71,7 +63,6 @@ struct ExtQueues {
     unsigned long long *unit_hits;  // seed hits per unit (statistics)
     unsigned long long *tile_hits;  // ... per unit and tile (K34 writes them, k34_sum_hits folds them into unit_hits)
     uint64_t cand_cap, follow_cap, med_cap, long_cap;   // follow_cap, med_cap: per shard (k4_queue.h: ShardMap)
-    uint64_t walk_cap;        // not used: a unit's walk-queue shards have FusedUnit::walk_cap entries (the field stays because K34's argument block embeds this struct)
     uint32_t ebits, dbits;
 };
 // bit 31 of a walk-queue entry's x (POS_MASK leaves it free): K34's first pass ran the sharp filter on this pair at its flush and

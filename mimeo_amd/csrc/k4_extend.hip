@@ -28,6 +28,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "k34.h"
 #include "k4_queue.h"
 
 namespace mimeo {
@@ -688,15 +689,11 @@ static uint32_t generic_grid() {
     return g_generic_grid;
 }
 
-// fused heavy kernel (k34_fused.hip)
-int launch_fused_batch(const FusedUnit *d_units, uint32_t nactive, const ExtQueues &q, const HeavyPlan &plan, const mimeo_params *p, hipStream_t st,
-                       uint32_t dbg);
-void launch_sum_hits(const ExtQueues &q, uint32_t nunits, hipStream_t st);
-
 static_assert(sizeof(Cand) == queue_plan::CAND_BYTES && sizeof(mimeo_hsp) == queue_plan::HSP_BYTES, "queue_plan.h prices the candidate and HSP slices with these sizes");
 
 void ExtBatch::release() {
-    for (DeviceBuf *b : {&units, &ctr, &nsel, &unit_hits, &tile_hits, &selfs, &hits, &bigcand, &bigacc, &heavy, &mirror, &funits, &nwalk_u, &plan_buf}) b->release();
+    for (DeviceBuf *b : {&units, &ctr, &nsel, &unit_hits, &tile_hits, &selfs, &hits, &bigcand, &bigacc, &mirror, &funits}) b->release();
+    if (k34_) { k34_->release(); delete k34_; k34_ = nullptr; }
     for (DeviceBuf &b : qbuf) b.release();   // slices: nothing is freed here
     for (DeviceBuf &b : sbuf) b.release();
     arena_q.release(); arena_s.release();
@@ -766,6 +763,8 @@ int ExtBatch::start(const std::vector<UnitWork> &work, const mimeo_params *p, co
     if (!nunits) return 0;
     w_ = work; p_ = *p;
     sw_ = read_switches();
+    // a switch that is silently ignored would falsify someone's profile: the timing experiments of this word are gone
+    if (sw_.k34_dbg & ~48u) { set_error("MIMEO_K34_DEBUG: only 16 (run members are kept) and 32 (no flush filter), or their sum, are switches"); return MIMEO_ERR_ARG; }
     uint64_t max_t = 0, max_q = 0;
     uint32_t launching = 0;
     expect_hits_ = 0;
@@ -889,30 +888,16 @@ int ExtBatch::enqueue_k34() {
     }
     const uint32_t nactive = nactive_ = (uint32_t)h_funits_.size();
     if (nactive) {
-        // the split pass's tile lists (number + estimate per slot) and its plan (dense tiles, part bases, splits, counters)
-        const size_t slots = (size_t)std::min(nactive, 32768u) * NTILE;
         int rc;
-        if ((rc = funits.reserve((size_t)nactive * sizeof(FusedUnit))) || (rc = nwalk_u.reserve((size_t)nactive * 9 * 8)) ||
-            (rc = heavy.reserve((size_t)nactive * NTILE * 12)) || (rc = plan_buf.reserve(slots * 28 + 4096)))
+        if (!k34_) k34_ = new K34Buffers();
+        if ((rc = funits.reserve((size_t)nactive * sizeof(FusedUnit))) || (rc = k34_->prepare(h_funits_, q, st)))
             return rc == MIMEO_ERR_NOMEM && splittable_ ? MIMEO_ERR_SPLIT : rc;
-        q.heavy_est = (unsigned long long *)heavy.p;
-        q.heavy = (uint32_t *)(q.heavy_est + (size_t)nactive * NTILE);
-        HeavyPlan plan;
-        plan.est = q.heavy_est;
-        plan.split = (uint4 *)plan_buf.p;                       // slots * 16
-        plan.tile = (uint2 *)(plan.split + slots);              // slots * 8
-        plan.base = (uint32_t *)(plan.tile + slots);            // (slots + 1) * 4
-        plan.ctr = (unsigned int *)(plan.base + slots + 4);     // 3 counters
-        plan_ctr_ = plan.ctr;
-        q.nwalk_u = (unsigned long long *)nwalk_u.p;            // 8 walk-queue shards per unit, then the split-pass tile counts
-        q.nheavy_u = q.nwalk_u + (size_t)nactive * 8;
         HIP_TRY(hipMemcpyAsync(funits.p, h_funits_.data(), (size_t)nactive * sizeof(FusedUnit), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(nwalk_u.p, 0, (size_t)nactive * 9 * 8, st));
         HIP_TRY(hipEventRecord(ev[4], st));
-        if ((rc = launch_fused_batch((const FusedUnit *)funits.p, nactive, q, plan, &p_, st, sw_.k34_dbg))) return rc;
+        if ((rc = launch_fused_batch(*k34_, (const FusedUnit *)funits.p, q, &p_, st, sw_.k34_dbg))) return rc;
         HIP_TRY(hipEventRecord(ev[5], st));
-        for (uint32_t u0 = 0; u0 < nactive; u0 += 32768u) {
-            const uint32_t nu = std::min(32768u, nactive - u0);
+        for (uint32_t u0 = 0; u0 < nactive; u0 += K34_LAUNCH_UNITS) {
+            const uint32_t nu = std::min(K34_LAUNCH_UNITS, nactive - u0);
             ExtQueues qq = q;
             qq.nwalk_u = q.nwalk_u + (size_t)u0 * 8;
             const FusedUnit *fu = (const FusedUnit *)funits.p + u0;
@@ -1005,13 +990,12 @@ int ExtBatch::entropy(ExtCounters *c) {
 }
 
 int ExtBatch::print_stats(const ExtCounters &c, uint64_t nf, uint64_t nm, bool over) {
-    if (sw_.k34_dbg & 8)
-        fprintf(stderr, "[k34] passed on because: left stop unproven %llu, right %llu, bound %llu, alarm %llu; ONLY alarm %llu, only left %llu, only right %llu, only bound %llu\n",
-                c.dbg[0], c.dbg[1], c.dbg[2], c.dbg[3], c.dbg[4], c.dbg[5], c.dbg[6], c.dbg[7]);
-    if (sw_.k4_stats && plan_ctr_ && nactive_) {
-        unsigned int pc[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpy(pc, plan_ctr_, 12, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[k34] split pass: %u tiles listed of %u, %u parts of ~131072 hits\n", pc[1], nactive_ * (unsigned)NTILE, pc[2]);
+    if (sw_.k4_stats && k34_ && nactive_) {
+        unsigned int tiles = 0, slots = 0, parts = 0;
+        unsigned long long part_hits = 0;
+        const int rc = k34_->split_stats(&tiles, &slots, &parts, &part_hits);
+        if (rc) return rc;
+        fprintf(stderr, "[k34] split pass: %u tiles listed of %u, %u parts of ~%llu hits\n", tiles, slots, parts, part_hits);
     }
     if (sw_.k4_stats)
         fprintf(stderr, "[k4] units %u walk queue %llu walked %llu generic %llu long %llu followers %llu candidates %llu hsps %llu%s\n", (uint32_t)w_.size(),

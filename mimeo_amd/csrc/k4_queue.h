@@ -7,7 +7,7 @@
 //     (ShardMap::at); its readers see the shards as one flat range (ShardMap::slot);
 //   * staged records are private to their wavefront; a wave barrier stands on both sides of the flush that lets other
 //     lanes read them (WaveQueue::flush).
-// K34's walk-queue flush (k34_fused.hip: flush_walk) filters inside its flush and is not built on this.
+// K34's walk-queue flush (k34_fused.hip: walk_flush) filters inside its flush and is not built on this.
 #pragma once
 #include "k4_device.h"
 

@@ -1,5 +1,5 @@
 // seed_window.h — "which of 32 consecutive seed-window starts may be a seed hit", written once (no HIP in here: the filters of
-// k34_fused.hip and k4_device.h instantiate it with the device's primitives, tests/sanitize/seed_window_check.cc with the host's).
+// k34_filter.h and k4_device.h instantiate it with the device's primitives, tests/sanitize/seed_window_check.cc with the host's).
 //
 // The input is a bit plane of mismatching columns n (two words, n0 = the lower 32 columns) and, for the exact rule, the plane of
 // transversions d.  The window that starts at column BASE + i covers the columns BASE + i + c of the care positions c of CARE;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Development aid (CPU): the first pass of K34 in its level form, lane by lane in Python — the middle-key cut of a two-segment tile,
 the 12-or-1 probes of a chunk, the level-by-level emission into the ring of 128 descriptors, the rounds of 64 — against the pairs a
-brute-force join of the tile gives (mimeo_amd/csrc/k34_fused.hip: do_tile, "level emission").  What it checks is the LOGIC the kernel was
+brute-force join of the tile gives (mimeo_amd/csrc/k34_fused.hip: emit_levels).  What it checks is the LOGIC the kernel was
 written from before it met a GPU: every pair exactly once, the ring never overwritten, at most 127 descriptors waiting.  The kernel itself
 is checked on the GPU (tests/test_gpu_segments.py)."""
 import numpy as np

@@ -19,7 +19,7 @@ for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_S
            "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS" \
            "SQ_WAVES SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_INSTS_VMEM_WR SQ_INSTS_FLAT SQ_ACTIVE_INST_FLAT"; do
   rm -rf $R/gpurun_out/pmc_tmp
-  MIMEO_K34_DEBUG=${DBG:-0} timeout -k 10 240 rocprofv3 --kernel-trace --pmc $set -d $TMPD -o run --output-format csv -- python3 $R/scripts/dev_unit.py 1e7 1000 > $PARTS/pass$i.log 2>&1 || { echo "pass $i ($set) failed: $?"; tail -5 $PARTS/pass$i.log; exit 1; }
+  timeout -k 10 240 rocprofv3 --kernel-trace --pmc $set -d $TMPD -o run --output-format csv -- python3 $R/scripts/dev_unit.py 1e7 1000 > $PARTS/pass$i.log 2>&1 || { echo "pass $i ($set) failed: $?"; tail -5 $PARTS/pass$i.log; exit 1; }
   f=$(find $R/gpurun_out/pmc_tmp -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] || { echo "pass $i ($set): no counter file"; exit 1; }
   cp "$f" $PARTS/pass$i.csv

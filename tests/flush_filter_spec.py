@@ -1,4 +1,4 @@
-"""The sharp filter that K34's first pass runs where it flushes its staged pairs (k34_fused.hip: pair_needs_walk_sharp), restated
+"""The sharp filter that K34's first pass runs where it flushes its staged pairs (k34_filter.h: pair_needs_walk_sharp), restated
 on seed FRAMES with numpy, and the cheap filter in front of it (pair_needs_walk) in the same form.
 
 TEST INFRASTRUCTURE.  A frame is the 192 columns [p - 109, p + 83) around a seed start p (common.h): column 109 is the seed's

@@ -290,7 +290,7 @@ K34_LEFT, K34_RIGHT = (24, 24, 24, 24), (24, 24, 16)
 
 
 def k34_proven_block(a, b, xdrop, widths, strict=True):
-    """pair_needs_walk's stop proof on one side (k34_fused.hip: bound_block2), from the column codes in walking order: the index of
+    """pair_needs_walk's stop proof on one side (k34_filter.h: bound_block2), from the column codes in walking order: the index of
     the first block after which the walk is proven to have stopped, None if none is, and whether `up + xdrop == lomax` held at
     a checkpoint.  Columns behind a sequence end are identical, as the planes' zero padding makes them."""
     up = lomax = lo = 0
@@ -339,7 +339,7 @@ K34_CARE10 = (0, 1, 2, 4, 7, 8, 11, 13, 15, 16)
 
 
 def k34_needs_walk(T, Q, t, d, xdrop, hspthresh, strict=True):
-    """pair_needs_walk (k34_fused.hip) restated for a hit at target t on diagonal q = t + d, transitions allowed, away from the
+    """pair_needs_walk (k34_filter.h) restated for a hit at target t on diagonal q = t + d, transitions allowed, away from the
     sequence ends and from N: False = the filter dismisses the hit.  A dismissal needs a stop proof on both sides, the bound of
     the two best prefixes below hspthresh, and no possible earlier seed hit of the diagonal (fewer than two mismatches on ten
     care positions) ending where the left walk arrives before its proven stop.  strict=False is the filter with `<=`."""

@@ -1,4 +1,4 @@
-"""The sharp filter at the walk-queue flush of K34's first pass (k34_fused.hip: flush_walk, pair_needs_walk_sharp).
+"""The sharp filter at the walk-queue flush of K34's first pass (k34_fused.hip: walk_flush; k34_filter.h: pair_needs_walk_sharp).
 
 A pair the first pass stages is looked at once more where the wavefront flushes its staging area — both frames fetched by entry
 number, the walk kernel's three proofs in frame coordinates — and only the survivors reach the walk queue, marked so that
@@ -173,6 +173,28 @@ def test_a_unit_that_uses_both_passes(eng, monkeypatch, capfd, shrink):
         assert 0 < d[2] <= n[2] < d[1], ('walked hits', d[2], n[2], d[1])
         if shrink:                  # (the arrays' followers may overflow the queues of the first attempt on their own)
             assert d[5] > 0 and n[5] > 0, ('reruns', d[5], n[5])
+    g.close()
+
+
+def test_the_switch_word_keeps_two_bits_and_refuses_the_rest(eng, monkeypatch):
+    """MIMEO_K34_DEBUG: 16 and 32 (and their sum) are the switches that remain, and change no record; any other bit — the timing
+    experiments that used to sit in the kernel's loops, or one that never existed — is an error that names the variable, not a
+    switch that is silently ignored."""
+    rng = np.random.default_rng(34)
+    seqs = [ACGT[rng.integers(0, 4, size=2000, dtype=np.uint8)] for _ in range(2)]
+    g = eng.Genome(['a', 'b'], seqs)
+    prm = eng.default_params(chain=0)
+    _set(monkeypatch, {})
+    ref = eng.ungapped_hsps(g, 0, g, 1, 0, prm)
+    for v in ('16', '32', '48'):
+        _set(monkeypatch, {'MIMEO_K34_DEBUG': v})
+        assert eng.ungapped_hsps(g, 0, g, 1, 0, prm).tobytes() == ref.tobytes(), v
+    for v in ('4', '64'):
+        _set(monkeypatch, {'MIMEO_K34_DEBUG': v})
+        with pytest.raises(RuntimeError, match='MIMEO_K34_DEBUG'):
+            eng.ungapped_hsps(g, 0, g, 1, 0, prm)
+    _set(monkeypatch, {})
+    assert eng.ungapped_hsps(g, 0, g, 1, 0, prm).tobytes() == ref.tobytes()
     g.close()
 
 

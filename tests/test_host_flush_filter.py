@@ -1,4 +1,4 @@
-"""The sharp filter of K34's walk-queue flush (tests/flush_filter_spec.py restates k34_fused.hip: pair_needs_walk_sharp) against
+"""The sharp filter of K34's walk-queue flush (tests/flush_filter_spec.py restates k34_filter.h: pair_needs_walk_sharp) against
 the exact walk of tests/spec_v1.py: a pair it dismisses must be one for which the exact walk emits nothing — no follower (no
 earlier seed hit of the diagonal ends where the left walk arrives), both walks over inside the frame (80 steps to the left of the
 seed end, 64 to the right), and a score below the threshold.  On the designed diagonals of tests/gapfree_cases.py, which put
