@@ -557,6 +557,74 @@ int mimeo_path_pileup(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */
                       mimeo_pileup_column *cols /* caller's, ncols entries, or NULL */, uint8_t *call /* caller's, ncols bytes, or NULL */);
 
 /*
+ * Insertion columns of a pileup (kernel K14): the bases that mimeo_path_pileup counts in ins_runs / ins_bases and leaves out of
+ * its call, piled up column by column and called.  A region's representative copy routinely lacks something that most of its
+ * family carries — a private deletion, a truncated segment; the rows of the pile then all insert at one target base, and this
+ * call says what they insert.  A consumer splices the called bytes into the call of mimeo_path_pileup.
+ *
+ * "Pileup v2, insertion columns".  T, Q, aln, n, path_first, blocks, nblocks, windows, nwin, items and nitems are exactly those
+ * of mimeo_path_pileup.  Site s is the position IN FRONT OF target base x of window `window`; it has ncols insertion columns, and
+ * column j of site s is entry icol_first[s] + j of `icols` and of `icall`, with icol_first the prefix sum of ncols over the sites
+ * and nicols its total, in 64 bits.  `voters` is the number of sequences that vote at the site, the region's own copy among them
+ * (depth + 1 of the pileup's column x, as a rule); only the call reads it.
+ *
+ * Counts.  Per item (aln, group, w0, w1) and site s with sites[s].window == group and w0 <= x < w1, where the record has a block
+ * b_k, k > 0, with p_k == x and dq_k > 0 (p_k and dq_k as for mimeo_path_window_stats: the end of the block before, and the query
+ * bases skipped) — the "never split, belongs to the column that holds p_k" rule of ins_runs:
+ *   res[s]      runs += 1, bases += dq_k, max_len = max(max_len, dq_k), and longer += 1 where dq_k > ncols;
+ *   icols       for j in [0, min(dq_k, ncols)), with y the base of the aligned query strand at b_{k-1}.q + b_{k-1}.len + j — the
+ *               bases, in the order, that mimeo_path_text puts over '-' — column icol_first[s] + j counts y under a / c / g / t,
+ *               or under n where y is not one of ACGT (the N plane decides first).  Runs are left-aligned: every run's first
+ *               inserted base votes in column 0.
+ * A site inside a deletion (p_k < x < b_k.t) gets nothing from that item, and so does a site at the record's first block start, at
+ * a block boundary with dq_k == 0, or off the alignment.  Where both sequences jump (dq_k > 0 and dt_k > 0) the run counts at p_k:
+ * insertions come before deletions, as everywhere else.
+ * What follows, and what a caller may rely on:
+ *   - res[s].runs and res[s].bases equal ins_runs and ins_bases of mimeo_path_pileup at column x of that window, for the same items;
+ *   - a + c + g + t + n of column j is the number of runs with dq > j: it does not increase with j;
+ *   - where longer == 0, the sum of a + c + g + t + n over the site's columns is `bases`;
+ *   - the counts are exact integers of 32 bits and depend on nothing but the sequences, the blocks, the items and the sites: not on
+ *     the grid, the slices, the cut into jobs or the order of the items.
+ *
+ * Call, per insertion column:
+ *   top     the largest of a, c, g, t; among equal counts the order is A, C, G, T;
+ *   total   a + c + g + t + n;
+ *   vg      voters > total ? voters - total : 0 — the gap vote: everyone at the site who has no j-th inserted base, the region's
+ *           own copy among them;
+ *   byte    the winner's upper-case letter where top > vg; otherwise 'N' where top == 0 and n > vg; otherwise '-'.
+ * A tie goes to the gap: the representative inserts nothing.  With voters = depth + 1, "2 * ins_runs > depth + 1" — the rule by
+ * which a consumer picks its sites — is exactly total > vg in column 0.
+ *
+ * ncols is 1 .. 1024 (INSERT_MAX_COLS).  That is ample: with the default gap penalties and y-drop a single gap run cannot exceed
+ * about (ydrop - gap_open) / gap_extend = 300 bases.  With other parameters a longer run is truncated to the site's columns and
+ * counted in `longer` (max_len says how long it was).
+ *
+ * Everything is checked on the host before anything is uploaded; a violation is MIMEO_ERR_ARG with a message that starts with
+ * "mimeo_path_insertions:" and names the site, the item, the window, or the record and the block: everything mimeo_path_pileup
+ * checks, in the same order; then per site window < nwin, start <= x < end, 1 <= ncols <= 1024, and the sites strictly increasing
+ * by (window, x).  nsites == 0 returns MIMEO_OK at once; nitems == 0 leaves zero counts and '-' bytes.  res, icols and icall may
+ * each be NULL.  Records and blocks go to the device in the same bounded slices as for mimeo_path_stats, and only the slices that
+ * an item asks for; the insertion columns are worked off in batches of a bounded number.
+ *
+ * A new symbol beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs it checks for the symbol.
+ */
+typedef struct mimeo_insert_site {
+    uint32_t window, x, ncols, voters;
+} mimeo_insert_site;                                           /* 16 bytes */
+typedef struct mimeo_insert_result {
+    uint32_t runs, bases, longer, max_len;
+} mimeo_insert_result;                                         /* 16 bytes */
+typedef struct mimeo_insert_column {
+    uint32_t a, c, g, t, n;
+} mimeo_insert_column;                                         /* 20 bytes */
+int mimeo_path_insertions(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, const mimeo_alignment *aln, uint64_t n,
+                          const uint64_t *path_first, const mimeo_path_block *blocks, uint64_t nblocks,
+                          const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items, uint64_t nitems,
+                          const mimeo_insert_site *sites, uint64_t nsites,
+                          mimeo_insert_result *res /* caller's, nsites entries, or NULL */,
+                          mimeo_insert_column *icols /* caller's, nicols entries, or NULL */, uint8_t *icall /* caller's, nicols bytes, or NULL */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  A left-out pair is a scaffold pair: EVERY entry of the

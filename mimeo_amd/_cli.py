@@ -103,6 +103,18 @@ def add_consensus(parser):
                              'the members of the family, the mean depth of the pile and the columns at which most copies carry an '
                              'insertion (which the consensus leaves out). Ready for mimeo filter and mimeo map. Off by default: without '
                              'it no path is computed. Nothing is written with --recycle when the alignment file exists.')
+    parser.add_argument('--consensusInsertions', action='store_true',
+                        help='With --consensus: where most copies carry an insertion in front of a column of the representative feature, '
+                             'pile up the inserted bases too and call them on the GPU, and put them into the record, so that a deletion '
+                             'private to the representative does not become the family\'s. The header then also reports inserted=<bases>. '
+                             'Every other output is unchanged. Off by default.')
+
+
+def check_consensus(parser, args):
+    """--consensusInsertions of `mimeo self` (parser.error exits with status 2, before the engine starts)"""
+    if args.consensusInsertions and args.consensus is None:
+        parser.error('--consensusInsertions needs --consensus')
+    return args
 
 
 def check_families(parser, args):

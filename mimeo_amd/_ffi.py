@@ -20,6 +20,7 @@ SYMBOLS = [
     'mimeo_genome_keep_indexes', 'mimeo_genome_drop_indexes', 'mimeo_genome_build_indexes', 'mimeo_coverage_bedgraph',
     'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths', 'mimeo_path_stats',
     'mimeo_path_window_stats', 'mimeo_path_text', 'mimeo_link_regions', 'mimeo_path_pileup',
+    'mimeo_path_insertions',
 ]
 
 
@@ -73,6 +74,10 @@ WINDOW_ITEM = np.dtype([(n, '<u4') for n in ('aln', 'group', 'w0', 'w1')])   # m
 WINDOW_STATS = np.dtype([(n, '<u8') for n in COLUMN_STATS.names])   # mimeo_window_stats, 64 bytes: the fields of mimeo_column_stats in 64 bits
 PILEUP_WINDOW = np.dtype([(n, '<u4') for n in ('tid', 'start', 'end')])   # mimeo_pileup_window, 12 bytes
 PILEUP_COLUMN = np.dtype([(n, '<u4') for n in ('a', 'c', 'g', 't', 'n', 'del', 'ins_runs', 'ins_bases')])   # mimeo_pileup_column, 32 bytes
+INSERT_SITE = np.dtype([(n, '<u4') for n in ('window', 'x', 'ncols', 'voters')])   # mimeo_insert_site, 16 bytes
+INSERT_RESULT = np.dtype([(n, '<u4') for n in ('runs', 'bases', 'longer', 'max_len')])   # mimeo_insert_result, 16 bytes
+INSERT_COLUMN = np.dtype([(n, '<u4') for n in ('a', 'c', 'g', 't', 'n')])   # mimeo_insert_column, 20 bytes
+INSERT_MAX_COLS = 1024   # insertion columns of one site, at most (include/mimeo_hip.h)
 DEPTH_RUN = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4'), ('depth', '<u4')])
 
 _lib = None
@@ -128,6 +133,8 @@ def load():
         lib.mimeo_link_regions.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp]
     if hasattr(lib, 'mimeo_path_pileup'):
         lib.mimeo_path_pileup.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, vp]
+    if hasattr(lib, 'mimeo_path_insertions'):
+        lib.mimeo_path_insertions.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

@@ -437,6 +437,20 @@ int mimeo_path_pileup(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_
     return path_pileup_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, windows, nwin, items, nitems, cols, call);
 }
 
+int mimeo_path_insertions(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first,
+                          const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
+                          uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, mimeo_insert_result *res, mimeo_insert_column *icols,
+                          uint8_t *icall) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!nsites) return MIMEO_OK;
+    if (!T || !sites || (nwin && !windows) || (nitems && !items) || (n && (!aln || !path_first)) || (nblocks && !blocks)) {
+        set_error("mimeo_path_insertions: null argument");
+        return MIMEO_ERR_ARG;
+    }
+    return path_insertions_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, windows, nwin, items, nitems, sites, nsites, res, icols, icall);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

@@ -376,5 +376,11 @@ int link_regions_device(const mimeo_genome *T, const mimeo_alignment *aln, uint6
 int path_pileup_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
                        const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
                        uint64_t nitems, mimeo_pileup_column *cols, uint8_t *call);
+// K14: the pile of the inserted bases at the sites of a pileup and a base called from each insertion column (k14_insertions.hip);
+// host in, host out.  Q is never null here, and nsites > 0; res, icols and icall may each be null.
+int path_insertions_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
+                           const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
+                           uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, mimeo_insert_result *res, mimeo_insert_column *icols,
+                           uint8_t *icall);
 
 }  // namespace mimeo

@@ -18,17 +18,18 @@ constexpr uint32_t JOB_ITEMS = 64;                   // items of a job, at most 
 constexpr uint64_t MAX_BATCH_COLUMNS = 1ull << 28;   // a job numbers the columns of its batch in 32 bits, eight counters each
 constexpr uint64_t MAX_WINDOW_ITEMS = 0xFFFFFFFFull; // items that may name one window: the counters are 32 bits
 
-// The windows against the target scaffolds.
-inline bool validate_windows(const std::vector<uint64_t> &len_t, const mimeo_pileup_window *windows, uint64_t nwin, std::string *msg) {
+// The windows against the target scaffolds.  `name`: the entry point the message starts with (mimeo_path_insertions,
+// insert_host.h, makes the same checks under its own name).
+inline bool validate_windows(const std::vector<uint64_t> &len_t, const mimeo_pileup_window *windows, uint64_t nwin, std::string *msg, const char *name = NAME) {
     char buf[320];
     auto fail = [&](uint64_t g, const char *what) {
-        snprintf(buf, sizeof buf, "%s: window %llu (tid %u, [%u, %u)): %s", NAME, (unsigned long long)g, windows[g].tid, windows[g].start, windows[g].end, what);
+        snprintf(buf, sizeof buf, "%s: window %llu (tid %u, [%u, %u)): %s", name, (unsigned long long)g, windows[g].tid, windows[g].start, windows[g].end, what);
         *msg = buf;
         return false;
     };
     if (!nwin) return true;
-    if (!windows) { *msg = std::string(NAME) + ": null argument"; return false; }
-    if (nwin > 0xFFFFFFFFull) { *msg = std::string(NAME) + ": more than 2^32 - 1 windows"; return false; }
+    if (!windows) { *msg = std::string(name) + ": null argument"; return false; }
+    if (nwin > 0xFFFFFFFFull) { *msg = std::string(name) + ": more than 2^32 - 1 windows"; return false; }
     for (uint64_t g = 0; g < nwin; g++) {
         const mimeo_pileup_window &w = windows[g];
         if (w.tid >= len_t.size()) return fail(g, "tid is not a scaffold of the target genome");
@@ -41,16 +42,16 @@ inline bool validate_windows(const std::vector<uint64_t> &len_t, const mimeo_pil
 // The items against the records and the windows; the paths and the windows have passed their checks.  max_window_items: a
 // window that more items name is refused (a counter of one of its columns could wrap).
 inline bool validate_items(const mimeo_alignment *aln, uint64_t n, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
-                           uint64_t nitems, std::string *msg, uint64_t max_window_items = MAX_WINDOW_ITEMS) {
+                           uint64_t nitems, std::string *msg, uint64_t max_window_items = MAX_WINDOW_ITEMS, const char *name = NAME) {
     char buf[320];
     auto fail = [&](uint64_t i, const char *what) {
         const mimeo_window_item &it = items[i];
-        snprintf(buf, sizeof buf, "%s: item %llu (aln %u, window %u, [%u, %u)): %s", NAME, (unsigned long long)i, it.aln, it.group, it.w0, it.w1, what);
+        snprintf(buf, sizeof buf, "%s: item %llu (aln %u, window %u, [%u, %u)): %s", name, (unsigned long long)i, it.aln, it.group, it.w0, it.w1, what);
         *msg = buf;
         return false;
     };
     if (!nitems) return true;
-    if (!items || (n && !aln)) { *msg = std::string(NAME) + ": null argument"; return false; }
+    if (!items || (n && !aln)) { *msg = std::string(name) + ": null argument"; return false; }
     for (uint64_t i = 0; i < nitems; i++) {
         const mimeo_window_item &it = items[i];
         if (it.aln >= n) return fail(i, "aln is not a record of the call");
@@ -64,7 +65,7 @@ inline bool validate_items(const mimeo_alignment *aln, uint64_t n, const mimeo_p
         std::vector<uint64_t> per(nwin, 0);
         for (uint64_t i = 0; i < nitems; i++)
             if (++per[items[i].group] > max_window_items) {
-                snprintf(buf, sizeof buf, "%s: window %u (tid %u, [%u, %u)): more than %llu items name it (item %llu): the counters are 32 bits", NAME,
+                snprintf(buf, sizeof buf, "%s: window %u (tid %u, [%u, %u)): more than %llu items name it (item %llu): the counters are 32 bits", name,
                          items[i].group, windows[items[i].group].tid, windows[items[i].group].start, windows[items[i].group].end,
                          (unsigned long long)max_window_items, (unsigned long long)i);
                 *msg = buf;

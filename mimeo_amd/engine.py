@@ -299,6 +299,47 @@ def pileup(A, B, records, first, blocks, windows, items, counts=True, call=True)
     return cols, letters
 
 
+def insertions(A, B, records, first, blocks, windows, items, sites, results=True, counts=True, call=True):
+    """The insertion columns of a pileup and a base called from each (mimeo_path_insertions, kernel K14): (res, icols, icall) —
+    res one _ffi.INSERT_RESULT row per site (the runs that insert in front of the site's target base, their bases, how many are
+    longer than the site's columns, and the longest), icols one _ffi.INSERT_COLUMN row and icall one byte per insertion column
+    (the inserted bases piled up left-aligned; the letter where it outvotes everyone who inserts nothing there, '-' otherwise;
+    include/mimeo_hip.h "pileup v2, insertion columns" has the rules).  The columns of site s start at entry sum(ncols of the
+    sites before it).  records / first / blocks / windows / items exactly as for pileup; sites: _ffi.INSERT_SITE rows (or an
+    (n, 4) array) of (window number, x, ncols, voters), strictly increasing by (window, x), as formats.insertion_sites makes
+    them.  results=False / counts=False / call=False: that array is not computed and None comes back in its place.  A bad path,
+    window, item or site is a RuntimeError naming it, raised before anything runs on the device."""
+    recs, first, blk = _paths(records, first, blocks)
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_path_insertions'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_path_insertions: rebuild the library')
+    win = np.asarray(windows)
+    if win.dtype != _ffi.PILEUP_WINDOW:
+        a = np.asarray(win, dtype=np.uint32).reshape(-1, 3)
+        win = np.zeros(a.shape[0], dtype=_ffi.PILEUP_WINDOW)
+        win['tid'], win['start'], win['end'] = a[:, 0], a[:, 1], a[:, 2]
+    win = np.ascontiguousarray(win)
+    it = _window_items(items)
+    st = np.asarray(sites)
+    if st.dtype != _ffi.INSERT_SITE:
+        a = np.asarray(st, dtype=np.uint32).reshape(-1, 4)
+        st = np.zeros(a.shape[0], dtype=_ffi.INSERT_SITE)
+        st['window'], st['x'], st['ncols'], st['voters'] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    st = np.ascontiguousarray(st)
+    # the arrays are sized by what the library will accept: a site with more than INSERT_MAX_COLS columns is refused there,
+    # before anything is written
+    nicols = int(np.minimum(st['ncols'].astype(np.int64), _ffi.INSERT_MAX_COLS).sum())
+    res = np.zeros(st.size, dtype=_ffi.INSERT_RESULT) if results else None
+    icols = np.zeros(nicols, dtype=_ffi.INSERT_COLUMN) if counts else None
+    icall = np.full(nicols, ord('-'), dtype=np.uint8) if call else None
+    _ffi.check(lib.mimeo_path_insertions(A._h, B._h if B is not None else None, recs.ctypes.data if recs.size else None, recs.size, first.ctypes.data,
+                                         blk.ctypes.data if blk.size else None, blk.size, win.ctypes.data if win.size else None, win.size,
+                                         it.ctypes.data if it.size else None, it.size, st.ctypes.data if st.size else None, st.size,
+                                         res.ctypes.data if results and st.size else None, icols.ctypes.data if counts and nicols else None,
+                                         icall.ctypes.data if call and nicols else None))
+    return res, icols, icall
+
+
 def path_text(A, B, records, first, blocks):
     """The text of alignment paths (mimeo_path_text, kernel K11): (row_first, trow, qrow) as numpy arrays (<u8, uint8, uint8).
     Row i is trow[row_first[i]:row_first[i + 1]] over the same range of qrow: the target's letters over the aligned query

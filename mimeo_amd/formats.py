@@ -477,7 +477,43 @@ PILEUP_DEPTH_FIELDS = ('a', 'c', 'g', 't', 'n', 'del')
 CONSENSUS_WIDTH = 60
 
 
-def consensus_records(regions, names_sorted, prefix, reps, cols, call, suffix='', number=1):
+INSERT_SITE = np.dtype([(n, '<u4') for n in ('window', 'x', 'ncols', 'voters')])   # _ffi.INSERT_SITE (this module does not load the library)
+INSERT_MAX_COLS = 1024   # _ffi.INSERT_MAX_COLS
+
+
+def _pileup_depth(c):
+    """a + c + g + t + n + del of _ffi.PILEUP_COLUMN rows, in 64 bits: the alignment rows over every column"""
+    return sum(c[f].astype(np.int64) for f in PILEUP_DEPTH_FIELDS) if len(c) else np.zeros(0, dtype=np.int64)
+
+
+def _ins_site_mask(c, depth):
+    """The ins_sites rule: the columns in front of which most of the pile inserts something, 2 * ins_runs > depth + 1 (the own
+    copy, which inserts nothing, counted in).  The one statement of it: the header's ins_sites= and insertion_sites share it."""
+    return 2 * c['ins_runs'].astype(np.int64) > depth + 1
+
+
+def insertion_sites(windows, cols):
+    """The sites of engine.insertions (kernel K14) from what engine.pileup returned for a run of windows: _ffi.INSERT_SITE rows,
+    one per column that the ins_sites rule picks (_ins_site_mask), in the order of the columns — strictly increasing by (window,
+    x).  windows: the _ffi.PILEUP_WINDOW rows of the pileup call; cols: its columns.  Per site window is the window's number in
+    the run, x the target base, voters = depth + 1 (the region's own copy votes), and ncols = min(ins_bases - ins_runs + 1,
+    _ffi.INSERT_MAX_COLS): each run has at least one base, so this bounds the longest run and no second ask is needed."""
+    win = np.asarray(windows)
+    n = win['end'].astype(np.int64) - win['start'].astype(np.int64)
+    depth = _pileup_depth(cols)
+    at = np.flatnonzero(_ins_site_mask(cols, depth)) if len(cols) else np.zeros(0, dtype=np.int64)
+    col_first = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    g = np.searchsorted(col_first, at, side='right') - 1   # an empty window has no column: 'right' steps over it
+    sites = np.zeros(at.size, dtype=INSERT_SITE)
+    if at.size:
+        sites['window'] = g
+        sites['x'] = win['start'].astype(np.int64)[g] + (at - col_first[g])
+        sites['ncols'] = np.minimum(cols['ins_bases'].astype(np.int64)[at] - cols['ins_runs'].astype(np.int64)[at] + 1, INSERT_MAX_COLS)
+        sites['voters'] = np.minimum(depth[at] + 1, 0xFFFFFFFF)
+    return sites
+
+
+def consensus_records(regions, names_sorted, prefix, reps, cols, call, suffix='', number=1, insertions=None):
     """--consensus: one FASTA record per family, in the order of family_lines' names.  reps: family_representatives; cols / call:
     what engine.pileup returned for the representatives' regions as windows, in the order of reps (window k starts at the summed
     length of the windows before it).  The sequence is the call bytes of the representative's window with '-' removed (a column
@@ -487,18 +523,35 @@ def consensus_records(regions, names_sorted, prefix, reps, cols, call, suffix=''
     (the alignment rows per base; the region's own copy is not counted), ins_sites the number of columns in front of which most
     of the pile inserts something: 2 * ins_runs > a + c + g + t + n + del + 1 (the own copy, which inserts nothing, counted
     in).  pileup v1 inserts nothing into the call; ins_sites says how often that matters.  number: that of the first family of
-    reps (a caller that works the families off in runs).  Returns the lines."""
+    reps (a caller that works the families off in runs).  insertions (--consensusInsertions; None: every line as without it):
+    (sites, icall) — the sites formats.insertion_sites picked for these windows (window numbers those of reps) and the bytes
+    engine.insertions called for their columns (kernel K14, "pileup v2"); the sequence of a window is then, for each column x in
+    order, the icall bytes of the site in front of x without '-' (where there is a site) followed by call[x] without '-', and
+    the header gains inserted=<bases>, the letters that came from icall, after ins_sites.  Returns the lines."""
     lines, at = [], 0
+    if insertions is not None:
+        sites, icall = insertions
+        icall = np.asarray(icall, dtype=np.uint8)
+        icol_first = np.concatenate([[0], np.cumsum(sites['ncols'].astype(np.int64))]).astype(np.int64)
     for k, (i, members) in enumerate(reps, number):
         r = regions[i]
         n = int(r['end']) - int(r['start'])
         c = cols[at:at + n]
-        depth = sum(c[f].astype(np.int64) for f in PILEUP_DEPTH_FIELDS) if n else np.zeros(0, dtype=np.int64)
-        seq = bytes(np.asarray(call[at:at + n], dtype=np.uint8).tobytes()).replace(b'-', b'').decode('ascii')
+        depth = _pileup_depth(c)
+        letters = np.asarray(call[at:at + n], dtype=np.uint8)
         at += n
-        lines.append('>F%d%s rep=%s_%05d %s:%d-%d members=%d length=%d mean_depth=%.2f ins_sites=%d' % (
+        more = ''
+        if insertions is not None:
+            s0, s1 = (int(v) for v in np.searchsorted(sites['window'], [k - number, k - number + 1], side='left'))
+            ins = icall[int(icol_first[s0]):int(icol_first[s1])]
+            # every byte of a site goes in front of column x - start: np.insert keeps the order of equal positions
+            where = np.repeat(sites['x'][s0:s1].astype(np.int64) - int(r['start']), sites['ncols'][s0:s1].astype(np.int64))
+            letters = np.insert(letters, where, ins)
+            more = ' inserted=%d' % int((ins != ord('-')).sum())
+        seq = letters.tobytes().replace(b'-', b'').decode('ascii')
+        lines.append('>F%d%s rep=%s_%05d %s:%d-%d members=%d length=%d mean_depth=%.2f ins_sites=%d%s' % (
             k, suffix, prefix, i + 1, names_sorted[int(r['chrom'])], int(r['start']), int(r['end']), members, len(seq),
-            float(depth.sum()) / n if n else 0.0, int((2 * c['ins_runs'].astype(np.int64) > depth + 1).sum()) if n else 0))
+            float(depth.sum()) / n if n else 0.0, int(_ins_site_mask(c, depth).sum()) if n else 0, more))
         lines.extend(seq[j:j + CONSENSUS_WIDTH] for j in range(0, len(seq), CONSENSUS_WIDTH))
     return lines
 

@@ -20,7 +20,7 @@ def mainArgs(argv=None):
                         help='Minimum depth of aligned segments from same scaffold to report feature. Used if "--strictSelf" mode is selected.')
     parser.add_argument('--strictSelf', action='store_true',
                         help='If set process same-scaffold alignments separately with option to use higher "--intraCov" threshold.')
-    return _cli.check_families(parser, _cli.check_common(parser, parser.parse_args(argv)))
+    return _cli.check_consensus(parser, _cli.check_families(parser, _cli.check_common(parser, parser.parse_args(argv))))
 
 
 def main(argv=None):
@@ -39,7 +39,7 @@ def main(argv=None):
                           label=args.label, prefix=args.prefix, dist=dist,
                           anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence,
                           region_stats=args.regionStats, maf=args.maf, cs=args.cs, families=args.families, family_cover=args.familyCover,
-                          consensus=args.consensus)
+                          consensus=args.consensus, consensus_insertions=args.consensusInsertions)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

@@ -294,11 +294,15 @@ def linked_regions(A, kept_paths, select, regions, cover):
 CONSENSUS_BUDGET = 1 << 22   # columns asked of engine.pileup at once: 128 MiB of counts on the host
 
 
-def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budget=CONSENSUS_BUDGET):
+def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budget=CONSENSUS_BUDGET, insertions=False):
     """--consensus for one block of GFF3 rows: the families exactly as family_block computes them, of every family the
     representative region (formats.family_representatives) as a window, the items of those regions (formats.region_items,
     without the trivial self rows) as the pile, engine.pileup (kernel K13) in runs of windows of at most `budget` columns (a
-    longer window goes alone), the lines of formats.consensus_records.  The lines do not depend on the budget."""
+    longer window goes alone), the lines of formats.consensus_records.  The lines do not depend on the budget.  insertions
+    (--consensusInsertions): per run of windows the sites in front of which most of the pile inserts something
+    (formats.insertion_sites), one engine.insertions call (kernel K14) over the same windows and items — none for a run without a
+    site — and its called bytes spliced into the records; a site where a run was longer than its columns is logged once, with
+    its family."""
     (recs, f2, b2), names_sorted, items, family, links = linked_regions(A, kept_paths, select, regions, cover)
     reps = formats.family_representatives(regions, family, links)
     tid_of = {n: i for i, n in enumerate(A.names)}
@@ -318,14 +322,26 @@ def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budge
         run = its[np.searchsorted(its['group'], g0, side='left'):np.searchsorted(its['group'], g1, side='left')].copy()
         run['group'] -= g0
         cols, call = engine.pileup(A, None, recs, f2, b2, windows[g0:g1], run)
-        lines += formats.consensus_records(regions, names_sorted, prefix, reps[g0:g1], cols, call, suffix=suffix, number=g0 + 1)
+        ins = None
+        if insertions:
+            sites = formats.insertion_sites(windows[g0:g1], cols)
+            ins = (sites, np.zeros(0, dtype=np.uint8))
+            if sites.size:
+                res, _, icall = engine.insertions(A, None, recs, f2, b2, windows[g0:g1], run, sites, counts=False)
+                ins = (sites, icall)
+                for s in np.flatnonzero(res['longer']).tolist():
+                    logging.warning('--consensusInsertions: family F%d%s: an inserted run of %d bases in front of base %d of its representative is '
+                                    'longer than the %d insertion columns of the site and was truncated',
+                                    g0 + int(sites['window'][s]) + 1, suffix, int(res['max_len'][s]), int(sites['x'][s]), int(sites['ncols'][s]))
+        lines += formats.consensus_records(regions, names_sorted, prefix, reps[g0:g1], cols, call, suffix=suffix, number=g0 + 1, insertions=ins)
     return lines
 
 
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
                  B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None, maf=None, cs=False,
-                 text_budget=TEXT_BUDGET, families=None, family_cover=80, consensus=None, consensus_budget=CONSENSUS_BUDGET):
+                 text_budget=TEXT_BUDGET, families=None, family_cover=80, consensus=None, consensus_budget=CONSENSUS_BUDGET,
+                 consensus_insertions=False):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
@@ -349,13 +365,19 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     the alignment rows over it are piled up per column in runs of at most consensus_budget columns, and a base is called from
     each column (include/mimeo_hip.h "pileup v1") — a repeat library for `mimeo filter` and `mimeo map`.  It asks the alignment
     call for the paths, runs on rank 0 and adds no collective; with splitSelf the intra block follows with F*_intra names;
-    nothing is written when the TAB is recycled or a pair is listed twice."""
+    nothing is written when the TAB is recycled or a pair is listed twice.  consensus_insertions (with consensus: ValueError
+    without it): where most of the rows over a representative insert something in front of a column, the inserted bases are piled
+    up and called too (--consensusInsertions; kernel K14, include/mimeo_hip.h "pileup v2, insertion columns") and go into the
+    record, so that a private deletion of the representative does not become the family's; on rank 0, no collective; every other
+    output is unchanged."""
     dist = dist or Dist()
     cs = cs and paf is not None
     if families is not None and B is not None:
         raise ValueError('families needs a self job: the regions and the queries must lie in one genome')
     if consensus is not None and B is not None:
         raise ValueError('consensus needs a self job: the regions and the queries must lie in one genome')
+    if consensus_insertions and consensus is None:
+        raise ValueError('consensus_insertions needs consensus: there is no library to insert into')
     if (families is not None or consensus is not None) and not 1 <= int(family_cover) <= 100:
         raise ValueError('family_cover must be in 1..100, not %r' % (family_cover,))
     kept_paths = None
@@ -438,9 +460,10 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
         else:
             none = np.zeros(0, dtype=engine._ffi.INTERVAL)
             cl = consensus_block(A, kept_paths, ~intra if splitSelf else np.ones(kept.shape[0], bool), reg_main[0] if reg_main else none, str(prefix),
-                                 int(family_cover), '', consensus_budget)
+                                 int(family_cover), '', consensus_budget, bool(consensus_insertions))
             if splitSelf:   # the intra block's families follow, as in --families
-                cl += consensus_block(A, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), int(family_cover), '_intra', consensus_budget)
+                cl += consensus_block(A, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), int(family_cover), '_intra', consensus_budget,
+                                      bool(consensus_insertions))
             with open(consensus, 'w') as f:
                 for line in cl:
                     f.write(line + '\n')
