@@ -278,15 +278,16 @@ constexpr int MIMEO_ERR_SPLIT = -100;   // internal: never crosses the C-ABI
 inline uint32_t ext_batch_max_units(uint64_t max_tlen, uint64_t max_qlen) { return queue_plan::max_units(max_tlen, max_qlen, SEED_LEN); }
 
 // K5/K6: one group = one (target scaffold, query scaffold, strand) with its HSP range
-constexpr int MAX_BATCH = 32;
+// K6 takes up to MAX_BATCH anchors per group and round, K6_ROUND_ANCHORS over all groups (k6_gapped.hip: gapped_setup, k6_pick)
+constexpr int MAX_BATCH = 128;
+constexpr uint32_t K6_ROUND_ANCHORS = 32768;
 struct Group {
     StrandView T, Q;
     uint32_t tid, qid, minus, nchain;
     uint64_t hsp_begin, hsp_end;
     uint32_t naln, overflow;
-    // K6 round state: anchors are taken in order, up to nbatch per round
+    // K6 round state: anchors are taken in order, nbatch of them in the round under way
     uint32_t next, nacc, nbatch, job0;
-    uint32_t batch[MAX_BATCH];
 };
 // K5 (k5_chain.hip): sort + chain + anchor order for every group
 int chain_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_hsps, const uint32_t *d_hsp_unit, uint64_t nhsps,

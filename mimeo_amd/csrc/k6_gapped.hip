@@ -22,8 +22,14 @@
 //     anchor to the end of the shorter one, the diagonal is optimal (every column already scores its
 //     maximum) and the DP is skipped — this is what makes the trivial (A,A) self alignment cheap.
 //   * jobs of different anchors are independent, only the skip rule is ordered: each round takes
-//     the next <= nbatch unskipped anchors of every group (k6_pick), extends them all (dp_round),
-//     then replays the skip rule in order over the batch (k6_resolve).
+//     the next unskipped anchors of every group, up to the take (k6_pick), extends them all (dp_round),
+//     then replays the skip rule in order over the batch (k6_resolve).  Every accepted alignment needs
+//     its DP, so a group ends in one round only if the take exceeds what it accepts: the take is the
+//     round's budget of K6_ROUND_ANCHORS over the groups, at most MAX_BATCH = 128 (a C4 group accepts
+//     ~30, at most 39 in a measured row; a C5MID group ~57, at most 72), and k6_pick's window of PICK_SCAN
+//     ranks is longer than their chains.  Anchors near a pending one wait (fragments of one
+//     copy), and past its first 32 of a round a group takes no anchor on a band of diagonals that several
+//     pending ones share (the HSPs of one long collinear alignment): scheduling only, results do not depend on it.
 //   * path rule (mimeo_params.anchor_rule = MIMEO_ANCHOR_PATH, opt-in): an anchor is skipped iff it is a diagonal step of
 //     the path of an earlier alignment.  After a round's DP kernels k6_trace (k6_trace.hip) re-runs the round's halves with a traceback,
 //     checks them against the first run and leaves each path as gap-free blocks; k6_pick / k6_resolve<true> test the
@@ -163,13 +169,26 @@ __device__ __forceinline__ bool skip_test(const mimeo_alignment *aln, uint32_t n
 // anchor that is NEAR a lower-ranked anchor whose DP is pending is deferred (twice at most): in the
 // next round it is normally inside that anchor's accepted box and never costs a DP.
 enum : uint8_t { A_NEW = 0, A_DONE = 1, A_SKIPPED = 2, A_ACCEPTED = 3 };
-constexpr uint32_t PICK_SCAN = 512;   // ranks looked at per round, from the first unfinalised one
+// ranks looked at per round, from the first unfinalised one: one wavefront walks them in turn, so a group of 10^6 anchors must not be
+// walked whole every round.  Whatever lies beyond the window costs a round of its own: the groups of a C4 row chain 480 HSPs on
+// average and up to 628 (C5MID: up to 596) and accept anchors of rank 512 and beyond (4 in a C4 row, 31 in C5MID)
+constexpr uint32_t PICK_SCAN = 2048;
 constexpr uint32_t NEAR_DIAG = 256, NEAR_POS = 8192, MAX_DEFER = 2;
+// The take of a round (bmax) is sized so that a group of unrelated repeat copies finishes in ONE round.  What the near test does not
+// see are the far-apart HSPs of one long collinear alignment (synteny, a self pair): every one of them scheduled runs the whole long
+// DP and is swallowed afterwards.  The first GUARD_FREE anchors a group schedules in a round are taken as ever; a further one waits
+// when GUARD_COUNT or more pending or scheduled anchors of the group lie within GUARD_DIAG diagonals of its own, at any distance.
+// A count, not one neighbour: the chained HSPs of unrelated copies are collinear too, and in a C4 row one in ten of the anchors past
+// a group's 32nd has ONE scheduled anchor within 4096 diagonals (none has three), while a collinear alignment puts most of the 32
+// there.  A band with fewer members than the count costs at most that many DPs more.  A round still schedules a group's first
+// GUARD_FREE free anchors, so the guard keeps no count of waits (MAX_DEFER bounds the near deferral only).
+constexpr uint32_t GUARD_FREE = 32, GUARD_DIAG = 4096, GUARD_COUNT = 4;
 
-__device__ __forceinline__ bool anchors_near(uint2 a, uint2 b) {
+// bit 0: b is near a (a fragment of the same repeat copy); bit 1: b's diagonal is within the guard's band of a's
+__device__ __forceinline__ uint32_t anchor_relation(uint2 a, uint2 b) {
     int32_t da = (int32_t)a.x - (int32_t)a.y, db = (int32_t)b.x - (int32_t)b.y;
     uint32_t dd = (uint32_t)abs(da - db), dp = a.x > b.x ? a.x - b.x : b.x - a.x;
-    return dd <= NEAR_DIAG && dp <= NEAR_POS;
+    return ((dd <= NEAR_DIAG && dp <= NEAR_POS) ? 1u : 0u) | (dd <= GUARD_DIAG ? 2u : 0u);
 }
 
 // one wave per group; PATH: the skip test is the path rule (P is unused otherwise)
@@ -191,13 +210,17 @@ __global__ __launch_bounds__(64) void k6_pick(Group *__restrict__ groups, const 
             continue;
         }
         // near an unfinalised lower-ranked anchor whose DP is done (earlier rounds) or scheduled (this round)?
-        bool susp = false;
+        uint32_t near = 0, band = 0;   // per lane: any near one, how many within the guard's band
         for (uint32_t r2 = first + lane; r2 < r; r2 += 64)
-            if (astate[b0 + r2] == A_DONE && anchors_near(a, anchors[b0 + r2])) susp = true;
-        if (lane < nb && anchors_near(a, anchors[b0 + sb[lane]])) susp = true;
-        if (__ballot(susp) && adefer[b0 + r] < MAX_DEFER) {
+            if (astate[b0 + r2] == A_DONE) { const uint32_t x = anchor_relation(a, anchors[b0 + r2]); near |= x & 1u; band += x >> 1; }
+        for (uint32_t k = lane; k < nb; k += 64) { const uint32_t x = anchor_relation(a, anchors[b0 + sb[k]]); near |= x & 1u; band += x >> 1; }
+        if (__ballot(near) && adefer[b0 + r] < MAX_DEFER) {
             if (lane == 0) adefer[b0 + r]++;
             continue;
+        }
+        if (nb >= GUARD_FREE) {   // the guard: a later round takes it, if it is not swallowed by then
+            for (int o = 32; o > 0; o >>= 1) band += __shfl_xor(band, o);
+            if (band >= GUARD_COUNT) continue;
         }
         if (lane == 0) sb[nb] = r;
         nb++;
@@ -220,6 +243,9 @@ __global__ __launch_bounds__(64) void k6_pick(Group *__restrict__ groups, const 
 
 // one wave per group: finalise anchors in rank order as far as DP results exist
 constexpr uint32_t RESOLVE_NEW = 256;  // boxes accepted per invocation that fit the LDS list
+// a round's take fits one invocation; with anchors left pending by earlier rounds an invocation may stop at the list's end, and the
+// next round (possibly one without jobs) goes on from there
+static_assert(RESOLVE_NEW >= (uint32_t)MAX_BATCH, "k6_resolve accepts a full take in one invocation");
 
 // bounded extensions: does the alignment of the anchor of rank `rank` (box o: tstart, tend, qstart, qend) put a bound
 // into the cells that the halves L / R of anchor a looked at?  Yes iff one of its blocks covers an evaluated row of a half
@@ -485,8 +511,30 @@ static int round_stats(uint32_t n, uint64_t nhsps, bool bounded, unsigned long l
     return 0;
 }
 
+// MIMEO_K6_STATS, after the last round: alignments accepted per group, which is what sizes MAX_BATCH (every accepted alignment needs its DP,
+// so a group that accepts more than the take cannot finish in one round)
+static int accepted_stats(const Group *d_groups, uint32_t ngroups, uint32_t bmax) {
+    std::vector<Group> hg(ngroups);
+    HIP_TRY(hipStreamSynchronize(stream()));
+    HIP_TRY(hipMemcpy(hg.data(), d_groups, (size_t)ngroups * sizeof(Group), hipMemcpyDeviceToHost));
+    unsigned long long hist[11] = {0}, sum = 0, over = 0;   // 0, 1, 2, 3-4, 5-8, ... 129-256, more
+    uint32_t mx = 0;
+    for (const Group &g : hg) {
+        uint32_t b = 0;
+        while (b < 10 && (b ? 1u << (b - 1) : 0u) < g.nacc) b++;
+        hist[b]++; sum += g.nacc; mx = std::max(mx, g.nacc); over += g.nacc > bmax ? 1u : 0u;
+    }
+    fprintf(stderr, "[k6] accepted per group: max %u mean %.2f of %u groups, %llu above the take of %u; 0 1 2 <=4 <=8 .. <=256 more:", mx,
+            (double)sum / ngroups, ngroups, over, bmax);
+    for (int b = 0; b < 11; b++) fprintf(stderr, " %llu", hist[b]);
+    fprintf(stderr, "\n");
+    return 0;
+}
+
 struct K6Call {   // what a gapped call runs with; gapped_device sets the mode, gapped_setup reads the development switches, once per call
-    uint32_t bmax, rounds;   // bmax: anchors per group and round (200 units: 32 -> one large round and a short one); MIMEO_K6_BMAX
+    // bmax: anchors per group and round, MIMEO_K6_BMAX.  The default is the round's budget over the groups, up to MAX_BATCH: above what any group
+    // of a C4 row or of C5MID accepts, so their rounds end with the groups' anchors, not with the take
+    uint32_t bmax, rounds;
     bool stats, path, bounded, box_paths;   // box_paths: the anchors' ranks are recorded; the halves are traced after the last round
     int32_t cap;             // of a score in 32-bit DP cells (below)
     uint64_t pool_budget;
@@ -496,9 +544,12 @@ struct K6Call {   // what a gapped call runs with; gapped_device sets the mode, 
 
 // switches, the buffers of a gapped call, the anchors
 static int gapped_setup(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, const uint32_t *d_order, uint64_t nhsps, K6Call &c) {
-    c.bmax = getenv("MIMEO_K6_BMAX") ? (uint32_t)atoi(getenv("MIMEO_K6_BMAX")) : 8192u / ngroups;
+    // the take: the round's anchor budget shared among the groups, at least 1 (thousands of small groups take few anchors each), at most
+    // the size of k6_pick's list.  200 groups of a C4 row: 163 -> MAX_BATCH
+    c.bmax = getenv("MIMEO_K6_BMAX") ? (uint32_t)atoi(getenv("MIMEO_K6_BMAX")) : K6_ROUND_ANCHORS / ngroups;
     c.bmax = c.bmax < 1 ? 1 : (c.bmax > MAX_BATCH ? MAX_BATCH : c.bmax);
     c.stats = getenv("MIMEO_K6_STATS") != nullptr;
+    if (c.stats) fprintf(stderr, "[k6] take %u anchors per group and round (%u groups, limit %d, budget %u)\n", c.bmax, ngroups, MAX_BATCH, K6_ROUND_ANCHORS);
     // 32-bit DP cells: beyond this score a half extension goes to (or, in k6_dp_any and k6_trace, rebases its cells in) the last kernel;
     // MIMEO_K6_SCORE_CAP lowers it so that tests of ordinary size take that road
     c.cap = getenv("MIMEO_K6_SCORE_CAP") ? std::max(100000, atoi(getenv("MIMEO_K6_SCORE_CAP"))) : 2000000000;
@@ -603,6 +654,7 @@ int gapped_device(Group *d_groups, uint32_t ngroups, const mimeo_hsp *d_sorted, 
         c.path = path; c.box_paths = want_paths && !path; c.bounded = path && p->bound_extensions;   // api.hip: bound_extensions needs the path rule
         if ((rc = gapped_setup(d_groups, ngroups, d_sorted, d_order, nhsps, c))) return rc;
         if ((rc = gapped_rounds(d_groups, ngroups, nhsps, p, d_aln, c))) return rc;
+        if (c.stats && (rc = accepted_stats(d_groups, ngroups, c.bmax))) return rc;
         if (c.path && c.stats) path_rule_stats(c);
         if (c.box_paths && (rc = paths_pass(d_groups, ngroups, p, c.cap, d_aln, c.pool_budget, c.stats))) return rc;
     }
