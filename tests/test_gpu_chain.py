@@ -6,7 +6,8 @@ Three kernels share the recurrence and its tie rule (earliest predecessor, earli
 of 2^24 HSPs and more).  MIMEO_K5_BIG_MIN / MIMEO_K5_BIG / MIMEO_K5_NO_BIG send the same HSPs through each of them.  The sets:
 random boxes, collinear runs (every HSP the next one's predecessor: nothing but inner dependencies), microsatellite-like
 rectangles (hundreds of HSPs that start or end on one base: waves and wide windows), all scores equal (ties everywhere), and sizes
-around the tile (64), the tree block (1024) and the window share boundaries."""
+around the tile (64), the tree block (1024) and the window share boundaries.  Which steps of the wave kernel these random sets reach,
+and designed sets for the edges they do not, are in tests/test_host_k5_wave.py and tests/test_gpu_k5_wave.py (tests/k5_wave_cases.py)."""
 import numpy as np
 import pytest
 
