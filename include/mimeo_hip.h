@@ -625,6 +625,70 @@ int mimeo_path_insertions(const mimeo_genome *T, const mimeo_genome *Q /* NULL: 
                           mimeo_insert_column *icols /* caller's, nicols entries, or NULL */, uint8_t *icall /* caller's, nicols bytes, or NULL */);
 
 /*
+ * The stacked rows of a pile (kernel K15): the evidence behind a consensus — for every item of a pileup one row of text in the
+ * coordinates of its window, with the insertion columns of the window's sites opened up, so that the rows of a window stand
+ * under each other as one multiple alignment (a Stockholm seed alignment per family is written from it).  mimeo_path_pileup
+ * reduces every column to eight counters and mimeo_path_text renders one pairwise row in that row's own columns; the host
+ * holds no sequence text, so the stack is made on the device from the resident genomes.
+ *
+ * "Pileup v3, the stack".  Everything up to nsites is word for word the argument list of mimeo_path_insertions, and the checks
+ * are the same, in the same order; only `voters` of a site is not read.
+ *
+ * Columns of a window.  Window g is [start, end); its sites are s_0 < ... < s_{m-1} at target bases x_i with n_i = ncols:
+ *   W_g           (end - start) + the sum of n_i, in 64 bits;
+ *   tcol of x     the column of target base x: (x - start) + the sum of n_i over the sites with x_i <= x;
+ *   insertion column j of site i   tcol of x_i - n_i + j: a site's columns sit directly in front of the column of its base.
+ *
+ * Rows.  Row k belongs to item k, in item order: rows[row_first[k] .. row_first[k + 1]), with row_first the 64-bit prefix sum
+ * of W of the item's window.  Each item has a row of its own, also where two items name the same record and window.
+ *
+ * Bytes of item k = (aln, group, w0, w1), with b_k, p_k, dt_k and dq_k as for mimeo_path_window_stats, lo = max of w0 and the
+ * first block's t, hi = min of w1 and the last block's end:
+ *   target column x    '.' where x lies outside [lo, hi), the record has no block, or lo >= hi;
+ *                      under block b_k: the letter of the aligned query strand at b_k.q + (x - b_k.t), in upper case, 'N' where
+ *                      the base is not one of ACGT (the N plane decides first);
+ *                      in a gap [p_k, b_k.t): '-';
+ *   insertion column j of site i   where w0 <= x_i < w1 and the record has a block b_k, k > 0, with p_k == x_i and j < dq_k: the
+ *                      letter of the aligned query strand at b_{k-1}.q + b_{k-1}.len + j in lower case, a c g t, or n — the
+ *                      bases, in the order, that mimeo_path_insertions counts; every other insertion column: '.'.
+ * An insertion column never holds '-' or an upper-case letter, a target column never a lower-case letter.
+ *
+ * res[k].  The item's query bases are the bases under its target columns in [w0, w1) and its insertion runs with
+ * w0 <= p_k < w1 (the "never split" rule): one contiguous stretch [q_lo, q_hi) of the aligned strand, in the coordinates of
+ * mimeo_path_block.q.  `bases` is the number of letters in the row, `hidden` the number of inserted bases of those runs that
+ * have no column: there is no site at p_k, or the run is longer than ncols.  bases + hidden == q_hi - q_lo always; all four
+ * fields are zero for an item without a query base.
+ *
+ * What a caller may rely on:
+ *   - per target column of a window, the numbers of A C G T N - over the rows of the window's items equal a c g t n del of
+ *     mimeo_path_pileup for the same items;
+ *   - per insertion column, the numbers of a c g t n equal icols of mimeo_path_insertions;
+ *   - the rows whose column 0 of a site holds a letter number res.runs of that site;
+ *   - where hidden == 0, the row's letters in order, upper-cased, are the slice [q_lo, q_hi) of the aligned strand as
+ *     mimeo_path_text writes it;
+ *   - the bytes depend on nothing but the sequences, blocks, windows, items and sites: not on slices, batches, jobs or the grid.
+ *
+ * Everything is checked on the host before anything is uploaded; a violation is MIMEO_ERR_ARG with a message that starts with
+ * "mimeo_path_stack:" and names the site, the item, the window, or the record and the block.  nitems == 0 returns MIMEO_OK with
+ * row_first holding one zero and rows NULL (also where no row has a column); nsites == 0 is legal and gives a stack without
+ * insertion columns.  res may be NULL.  row_first and rows are allocated by the library and released with mimeo_free.  Records
+ * and blocks go to the device in the same bounded slices as for mimeo_path_stats, and only the slices that an item asks for;
+ * the rows pass through a device buffer of bounded size (a single row goes in whole), so a call of any size runs in the memory
+ * that is free next to the genomes; the host arrays hold the whole call, and a caller bounds those by what it asks for at once.
+ *
+ * A new symbol beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs it checks for the symbol.
+ */
+typedef struct mimeo_stack_row {
+    uint32_t q_lo, q_hi, bases, hidden;
+} mimeo_stack_row;                                             /* 16 bytes */
+int mimeo_path_stack(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, const mimeo_alignment *aln, uint64_t n,
+                     const uint64_t *path_first, const mimeo_path_block *blocks, uint64_t nblocks,
+                     const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items, uint64_t nitems,
+                     const mimeo_insert_site *sites, uint64_t nsites,
+                     mimeo_stack_row *res /* caller's, nitems entries, or NULL */,
+                     uint64_t **row_first /* nitems + 1 */, uint8_t **rows /* row_first[nitems] bytes */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  A left-out pair is a scaffold pair: EVERY entry of the

@@ -110,6 +110,19 @@ def add_consensus(parser):
                              'Every other output is unchanged. Off by default.')
 
 
+def add_family_alignments(parser):
+    """--familyAlignments of `mimeo self` (`mimeo x` has its query in another genome)"""
+    parser.add_argument('--familyAlignments', type=str, default=None, metavar='FILE',
+                        help='Also write the evidence behind the repeat library to FILE: one Stockholm 1.0 block per repeat family (the '
+                             'families of --families; --familyCover applies; neither --families nor --consensus need be given), named '
+                             'F1, F2, ... (with --strictSelf the same-scaffold block follows as F1_intra, ...). A block holds the '
+                             'representative feature\'s own row and one row per alignment that piles up on it, named '
+                             '<seqid>/<start>-<end> (start > end on the minus strand), in the representative\'s coordinates with the '
+                             'columns that copies insert opened up (lower case), the #=GC RF line marking the representative\'s columns '
+                             'and #=GC cons the consensus of --consensus --consensusInsertions. The rows are made on the GPU. Ready for '
+                             'a profile-HMM builder. Off by default. Nothing is written with --recycle when the alignment file exists.')
+
+
 def check_consensus(parser, args):
     """--consensusInsertions of `mimeo self` (parser.error exits with status 2, before the engine starts)"""
     if args.consensusInsertions and args.consensus is None:

@@ -451,6 +451,20 @@ int mimeo_path_insertions(const mimeo_genome *T, const mimeo_genome *Q, const mi
     return path_insertions_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, windows, nwin, items, nitems, sites, nsites, res, icols, icall);
 }
 
+int mimeo_path_stack(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first,
+                     const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
+                     uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, mimeo_stack_row *res, uint64_t **row_first, uint8_t **rows) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!row_first || !rows) { set_error("mimeo_path_stack: null argument"); return MIMEO_ERR_ARG; }
+    *row_first = nullptr; *rows = nullptr;
+    if (!T || (nsites && !sites) || (nwin && !windows) || (nitems && !items) || (n && (!aln || !path_first)) || (nblocks && !blocks)) {
+        set_error("mimeo_path_stack: null argument");
+        return MIMEO_ERR_ARG;
+    }
+    return path_stack_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, windows, nwin, items, nitems, sites, nsites, res, row_first, rows);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

@@ -383,5 +383,10 @@ int path_insertions_device(const mimeo_genome *T, const mimeo_genome *Q, const m
                            const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
                            uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, mimeo_insert_result *res, mimeo_insert_column *icols,
                            uint8_t *icall);
+// K15: one row of text per item of a pileup, in its window's columns with the sites' insertion columns opened up (k15_stack.hip);
+// host in, two malloc'ed arrays out (and res, the caller's, which may be null).  Q is never null here.
+int path_stack_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
+                      const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
+                      uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, mimeo_stack_row *res, uint64_t **row_first, uint8_t **rows);
 
 }  // namespace mimeo

@@ -23,17 +23,19 @@ constexpr uint32_t JOB_ITEMS = 64;                   // entries of a job, at mos
 constexpr uint64_t MAX_BATCH_COLUMNS = 1ull << 28;   // a job numbers the columns of its batch in 32 bits, five counters each
 static_assert(INSERT_MAX_COLS <= TILE_COLS, "a site is never split: it fits a tile");
 
-// The sites against the windows, which have passed their checks.
-inline bool validate_sites(const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_insert_site *sites, uint64_t nsites, std::string *msg) {
+// The sites against the windows, which have passed their checks.  `name`: the entry point the message starts with
+// (mimeo_path_stack, stack_host.h, makes the same checks under its own name).
+inline bool validate_sites(const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_insert_site *sites, uint64_t nsites, std::string *msg,
+                           const char *name = NAME) {
     char buf[320];
     auto fail = [&](uint64_t s, const char *what) {
-        snprintf(buf, sizeof buf, "%s: site %llu (window %u, x %u, ncols %u): %s", NAME, (unsigned long long)s, sites[s].window, sites[s].x, sites[s].ncols, what);
+        snprintf(buf, sizeof buf, "%s: site %llu (window %u, x %u, ncols %u): %s", name, (unsigned long long)s, sites[s].window, sites[s].x, sites[s].ncols, what);
         *msg = buf;
         return false;
     };
     if (!nsites) return true;
-    if (!sites) { *msg = std::string(NAME) + ": null argument"; return false; }
-    if (nsites > 0xFFFFFFFFull) { *msg = std::string(NAME) + ": more than 2^32 - 1 sites"; return false; }
+    if (!sites) { *msg = std::string(name) + ": null argument"; return false; }
+    if (nsites > 0xFFFFFFFFull) { *msg = std::string(name) + ": more than 2^32 - 1 sites"; return false; }
     for (uint64_t s = 0; s < nsites; s++) {
         const mimeo_insert_site &v = sites[s];
         if (v.window >= nwin) return fail(s, "window is not below nwin");
@@ -50,9 +52,9 @@ inline bool validate_sites(const mimeo_pileup_window *windows, uint64_t nwin, co
 inline bool validate(const std::vector<uint64_t> &len_t, const std::vector<uint64_t> &len_q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
                      const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
                      uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, std::string *msg,
-                     uint64_t max_window_items = pileup_host::MAX_WINDOW_ITEMS) {
-    return path_stats_host::validate(len_t, len_q, aln, n, first, blocks, nblocks, msg, NAME) && pileup_host::validate_windows(len_t, windows, nwin, msg, NAME) &&
-           pileup_host::validate_items(aln, n, windows, nwin, items, nitems, msg, max_window_items, NAME) && validate_sites(windows, nwin, sites, nsites, msg);
+                     uint64_t max_window_items = pileup_host::MAX_WINDOW_ITEMS, const char *name = NAME) {
+    return path_stats_host::validate(len_t, len_q, aln, n, first, blocks, nblocks, msg, name) && pileup_host::validate_windows(len_t, windows, nwin, msg, name) &&
+           pileup_host::validate_items(aln, n, windows, nwin, items, nitems, msg, max_window_items, name) && validate_sites(windows, nwin, sites, nsites, msg, name);
 }
 
 // One site tile: the consecutive sites [site0, site0 + nsites) of one window, whose columns are the entries

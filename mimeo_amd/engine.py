@@ -340,6 +340,42 @@ def insertions(A, B, records, first, blocks, windows, items, sites, results=True
     return res, icols, icall
 
 
+def stack(A, B, records, first, blocks, windows, items, sites):
+    """The stacked rows of a pile (mimeo_path_stack, kernel K15): (res, row_first, rows) — row k, rows[row_first[k]:row_first[k + 1]],
+    is item k as text in the columns of its window with the insertion columns of the window's sites opened up in front of their
+    bases: A C G T N under a block, '-' in a gap of the path, '.' where the item does not reach, a c g t n in an insertion column
+    (include/mimeo_hip.h "pileup v3, the stack" has the rules); res one _ffi.STACK_ROW row per item: the stretch [q_lo, q_hi) of
+    the aligned query strand that the row shows, its letters, and the inserted bases that have no column.  records / first /
+    blocks / windows / items / sites exactly as for insertions (voters is not read; no site at all is legal).  The arrays hold the
+    whole call: a caller bounds them by what it asks for at once (workflow.alignment_block).  A bad path, window, item or site
+    is a RuntimeError naming it, raised before anything runs on the device."""
+    recs, first, blk = _paths(records, first, blocks)
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_path_stack'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_path_stack: rebuild the library')
+    win = np.asarray(windows)
+    if win.dtype != _ffi.PILEUP_WINDOW:
+        a = np.asarray(win, dtype=np.uint32).reshape(-1, 3)
+        win = np.zeros(a.shape[0], dtype=_ffi.PILEUP_WINDOW)
+        win['tid'], win['start'], win['end'] = a[:, 0], a[:, 1], a[:, 2]
+    win = np.ascontiguousarray(win)
+    it = _window_items(items)
+    st = np.asarray(sites)
+    if st.dtype != _ffi.INSERT_SITE:
+        a = np.asarray(st, dtype=np.uint32).reshape(-1, 4)
+        st = np.zeros(a.shape[0], dtype=_ffi.INSERT_SITE)
+        st['window'], st['x'], st['ncols'], st['voters'] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    st = np.ascontiguousarray(st)
+    res = np.zeros(it.size, dtype=_ffi.STACK_ROW)
+    pf, pr = C.c_void_p(), C.c_void_p()
+    _ffi.check(lib.mimeo_path_stack(A._h, B._h if B is not None else None, recs.ctypes.data if recs.size else None, recs.size, first.ctypes.data,
+                                    blk.ctypes.data if blk.size else None, blk.size, win.ctypes.data if win.size else None, win.size,
+                                    it.ctypes.data if it.size else None, it.size, st.ctypes.data if st.size else None, st.size,
+                                    res.ctypes.data if it.size else None, C.byref(pf), C.byref(pr)))
+    row_first = _ffi.take(pf, C.c_uint64(it.size + 1), np.dtype('<u8'))
+    return res, row_first, _ffi.take(pr, C.c_uint64(int(row_first[-1])), np.dtype(np.uint8))
+
+
 def path_text(A, B, records, first, blocks):
     """The text of alignment paths (mimeo_path_text, kernel K11): (row_first, trow, qrow) as numpy arrays (<u8, uint8, uint8).
     Row i is trow[row_first[i]:row_first[i + 1]] over the same range of qrow: the target's letters over the aligned query

@@ -556,6 +556,88 @@ def consensus_records(regions, names_sorted, prefix, reps, cols, call, suffix=''
     return lines
 
 
+def stack_sites(windows, cols, max_len=None):
+    """The sites of engine.stack (kernel K15) for --familyAlignments from what engine.pileup returned for a run of windows:
+    _ffi.INSERT_SITE rows, one per column in front of which ANY row of the pile inserts something (ins_runs > 0, not only the
+    majority sites of insertion_sites), in the order of the columns.  voters = depth + 1 as in insertion_sites.  max_len: per
+    site the longest run (mimeo_insert_result.max_len of an engine.insertions call over these sites): ncols = min(max_len,
+    _ffi.INSERT_MAX_COLS), so that no insertion column is empty; None: ncols = 1, the sites of that first call."""
+    win = np.asarray(windows)
+    n = win['end'].astype(np.int64) - win['start'].astype(np.int64)
+    at = np.flatnonzero(cols['ins_runs'] > 0) if len(cols) else np.zeros(0, dtype=np.int64)
+    col_first = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    g = np.searchsorted(col_first, at, side='right') - 1   # an empty window has no column: 'right' steps over it
+    sites = np.zeros(at.size, dtype=INSERT_SITE)
+    if at.size:
+        sites['window'] = g
+        sites['x'] = win['start'].astype(np.int64)[g] + (at - col_first[g])
+        sites['ncols'] = 1 if max_len is None else np.clip(np.asarray(max_len, dtype=np.int64), 1, INSERT_MAX_COLS)
+        sites['voters'] = np.minimum(_pileup_depth(cols)[at] + 1, 0xFFFFFFFF)
+    return sites
+
+
+def stockholm_row_name(qname, qlen, qstrand, q_lo, q_hi):
+    """<qname>/<s>-<e> of a row of stockholm_blocks: the stretch [q_lo, q_hi) of the aligned strand (engine.stack's res) on the
+    query's plus strand, 1-based inclusive; for a minus-strand row s > e, the Pfam / Rfam convention."""
+    if qstrand:
+        return '%s/%d-%d' % (qname, qlen - q_lo, qlen - q_hi + 1)
+    return '%s/%d-%d' % (qname, q_lo + 1, q_hi)
+
+
+def stockholm_blocks(regions, names_sorted, prefix, reps, sites, own, call, icall, rows, suffix='', number=1):
+    """--familyAlignments: one Stockholm 1.0 block per family, in the order of family_lines' names — the copies behind a
+    consensus record as one alignment in the representative's coordinates.  reps: family_representatives, whose regions are the
+    windows 0, 1, ... of this run; sites: the _ffi.INSERT_SITE rows of these windows (stack_sites: window numbers those of
+    reps), whose ncols insertion columns stand directly in front of the column of their base x; own: the representative's own
+    letters and call: the consensus byte (engine.pileup) per target column of the windows, one behind the other; icall: the
+    consensus byte per insertion column of the sites (engine.insertions); rows: per sequence row (window number, name, text) in
+    the order of the file, text the W bytes of engine.stack's row and name stockholm_row_name's.  A block is
+        # STOCKHOLM 1.0
+        #=GF ID F3
+        #=GF DE rep=<ID> <seqid>:<start>-<end> members=<m> rows=<r> columns=<W>
+        <seqid>/<start+1>-<end> <the representative's own row: its letters, '.' at insertion columns>
+        <name> <text>                 one per row of the window
+        #=GC RF <x at target columns, . at insertion columns>
+        #=GC cons <call at target columns; icall at insertion columns, its '-' written '.'>
+        //
+    rows= counts the sequence lines, the representative's own among them; a name that repeats inside a block gets .2, .3, ...
+    in order.  With '.' and '-' removed the cons line is the record of consensus_records with insertions for the same family.
+    number: that of the first family of reps.  Returns the lines."""
+    lines, at = [], 0
+    icall = np.asarray(icall, dtype=np.uint8)
+    icol_first = np.concatenate([[0], np.cumsum(sites['ncols'].astype(np.int64))]).astype(np.int64)
+    by_window = {}
+    for g, name, text in rows:
+        by_window.setdefault(int(g), []).append((name, text))
+    for k, (i, members) in enumerate(reps, number):
+        r = regions[i]
+        n = int(r['end']) - int(r['start'])
+        s0, s1 = (int(v) for v in np.searchsorted(sites['window'], [k - number, k - number + 1], side='left'))
+        ins = icall[int(icol_first[s0]):int(icol_first[s1])]
+        # every column of a site goes in front of column x - start: np.insert keeps the order of equal positions
+        where = np.repeat(sites['x'][s0:s1].astype(np.int64) - int(r['start']), sites['ncols'][s0:s1].astype(np.int64))
+        dots = np.full(ins.size, ord('.'), dtype=np.uint8)
+        open_up = lambda target, inserted: np.insert(np.asarray(target, dtype=np.uint8), where, inserted).tobytes().decode('ascii')
+        seqid = names_sorted[int(r['chrom'])]
+        mine = by_window.get(k - number, [])
+        seq = [('%s/%d-%d' % (seqid, int(r['start']) + 1, int(r['end'])), open_up(own[at:at + n], dots))]
+        seq += [(name, bytes(text).decode('ascii')) for name, text in mine]
+        width = n + ins.size
+        lines += ['# STOCKHOLM 1.0', '#=GF ID F%d%s' % (k, suffix),
+                  '#=GF DE rep=%s_%05d %s:%d-%d members=%d rows=%d columns=%d' % (prefix, i + 1, seqid, int(r['start']), int(r['end']), members, len(seq), width)]
+        seen = {}
+        for name, text in seq:
+            if len(text) != width:
+                raise ValueError('row %s has %d bytes for a block of %d columns' % (name, len(text), width))
+            seen[name] = seen.get(name, 0) + 1
+            lines.append('%s %s' % (name if seen[name] == 1 else '%s.%d' % (name, seen[name]), text))
+        lines.append('#=GC RF ' + open_up(np.full(n, ord('x'), dtype=np.uint8), dots))
+        lines.append('#=GC cons ' + open_up(call[at:at + n], np.where(ins == ord('-'), ord('.'), ins).astype(np.uint8)))
+        lines.append('//')
+        at += n
+    return lines
+
+
 def import_align(tab_rows, prefix=None, min_len=100, min_idt=95):
     """wrappers.py:33-117 import_Align: re-filter on int(end)-int(start) and float(pID); sort on
     the STRING columns tName, tStart, tEnd, tStrand (lexicographic, stable); UID = prefix_<rank>

@@ -294,16 +294,12 @@ def linked_regions(A, kept_paths, select, regions, cover):
 CONSENSUS_BUDGET = 1 << 22   # columns asked of engine.pileup at once: 128 MiB of counts on the host
 
 
-def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budget=CONSENSUS_BUDGET, insertions=False):
-    """--consensus for one block of GFF3 rows: the families exactly as family_block computes them, of every family the
-    representative region (formats.family_representatives) as a window, the items of those regions (formats.region_items,
-    without the trivial self rows) as the pile, engine.pileup (kernel K13) in runs of windows of at most `budget` columns (a
-    longer window goes alone), the lines of formats.consensus_records.  The lines do not depend on the budget.  insertions
-    (--consensusInsertions): per run of windows the sites in front of which most of the pile inserts something
-    (formats.insertion_sites), one engine.insertions call (kernel K14) over the same windows and items — none for a run without a
-    site — and its called bytes spliced into the records; a site where a run was longer than its columns is logged once, with
-    its family."""
-    (recs, f2, b2), names_sorted, items, family, links = linked_regions(A, kept_paths, select, regions, cover)
+def family_piles(A, kept_paths, select, regions, cover):
+    """What --consensus and --familyAlignments share for one block of GFF3 rows: the families exactly as family_block computes
+    them (linked_regions), of every family the representative region (formats.family_representatives) as a window, and the
+    items of those regions (formats.region_items, without the trivial self rows) as the piles, sorted by window.  Returns
+    ((records, first, blocks) of the rows, the sorted names, reps, windows, items)."""
+    paths, names_sorted, items, family, links = linked_regions(A, kept_paths, select, regions, cover)
     reps = formats.family_representatives(regions, family, links)
     tid_of = {n: i for i, n in enumerate(A.names)}
     rep = np.array([i for i, _ in reps], dtype=np.int64)
@@ -317,6 +313,19 @@ def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budge
     its = its.copy()
     its['group'] = window_of[its['group'].astype(np.int64)]
     its = its[np.argsort(its['group'], kind='stable')]
+    return paths, names_sorted, reps, windows, its
+
+
+def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budget=CONSENSUS_BUDGET, insertions=False):
+    """--consensus for one block of GFF3 rows: the families exactly as family_block computes them, of every family the
+    representative region (formats.family_representatives) as a window, the items of those regions (formats.region_items,
+    without the trivial self rows) as the pile (family_piles), engine.pileup (kernel K13) in runs of windows of at most `budget`
+    columns (a longer window goes alone), the lines of formats.consensus_records.  The lines do not depend on the budget.  insertions
+    (--consensusInsertions): per run of windows the sites in front of which most of the pile inserts something
+    (formats.insertion_sites), one engine.insertions call (kernel K14) over the same windows and items — none for a run without a
+    site — and its called bytes spliced into the records; a site where a run was longer than its columns is logged once, with
+    its family."""
+    (recs, f2, b2), names_sorted, reps, windows, its = family_piles(A, kept_paths, select, regions, cover)
     lines = []
     for g0, g1 in text_runs(windows['end'].astype(np.int64) - windows['start'], budget):
         run = its[np.searchsorted(its['group'], g0, side='left'):np.searchsorted(its['group'], g1, side='left')].copy()
@@ -337,11 +346,53 @@ def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budge
     return lines
 
 
+STACK_BUDGET = 1 << 26   # row bytes asked of engine.stack at once (one row goes whatever its size)
+
+
+def alignment_block(A, kept_paths, select, regions, prefix, cover, suffix, budget=CONSENSUS_BUDGET, stack_budget=STACK_BUDGET):
+    """--familyAlignments for one block of GFF3 rows: the families, representatives, windows and piles of consensus_block
+    (family_piles), and per run of windows of at most `budget` columns: engine.pileup (kernel K13) for the counts and the call,
+    and once more without items for the representative's own letters; the sites (formats.stack_sites: every column in front of
+    which a row inserts something, with as many columns as its longest run, which a first engine.insertions call over the
+    sites reports); engine.insertions (kernel K14) for the call of the insertion columns; and engine.stack (kernel K15) for the
+    rows, in runs of items of at most stack_budget bytes (one row goes whatever its size).  Returns the lines of
+    formats.stockholm_blocks; they depend on neither budget.  A row with hidden bases (a run beyond the 1024 columns of a site)
+    is logged once, with its family."""
+    (recs, f2, b2), names_sorted, reps, windows, its = family_piles(A, kept_paths, select, regions, cover)
+    lines = []
+    for g0, g1 in text_runs(windows['end'].astype(np.int64) - windows['start'], budget):
+        win = windows[g0:g1]
+        run = its[np.searchsorted(its['group'], g0, side='left'):np.searchsorted(its['group'], g1, side='left')].copy()
+        run['group'] -= g0
+        cols, call = engine.pileup(A, None, recs, f2, b2, win, run)
+        _, own = engine.pileup(A, None, recs, f2, b2, win, run[:0], counts=False)
+        sites = formats.stack_sites(win, cols)
+        icall = np.zeros(0, dtype=np.uint8)
+        if sites.size:
+            res, _, _ = engine.insertions(A, None, recs, f2, b2, win, run, sites, counts=False, call=False)
+            sites = formats.stack_sites(win, cols, max_len=res['max_len'])
+            _, _, icall = engine.insertions(A, None, recs, f2, b2, win, run, sites, results=False, counts=False)
+        width = (win['end'].astype(np.int64) - win['start']) + np.bincount(sites['window'], weights=sites['ncols'], minlength=g1 - g0).astype(np.int64)
+        rows = []
+        for i0, i1 in text_runs(width[run['group'].astype(np.int64)] if run.size else np.zeros(0, dtype=np.int64), stack_budget):
+            res, row_first, text = engine.stack(A, None, recs, f2, b2, win, run[i0:i1], sites)
+            for k in np.flatnonzero(res['bases']).tolist():
+                it, r = run[i0 + k], res[k]
+                qid = int(recs['qid'][int(it['aln'])])
+                name = formats.stockholm_row_name(A.names[qid], int(A.lengths[qid]), int(recs['qstrand'][int(it['aln'])]), int(r['q_lo']), int(r['q_hi']))
+                rows.append((int(it['group']), name, text[int(row_first[k]):int(row_first[k + 1])]))
+                if r['hidden']:
+                    logging.warning('--familyAlignments: family F%d%s: row %s has %d inserted bases beyond the insertion columns of its sites; they are '
+                                    'not shown', g0 + int(it['group']) + 1, suffix, name, int(r['hidden']))
+        lines += formats.stockholm_blocks(regions, names_sorted, prefix, reps[g0:g1], sites, own, call, icall, rows, suffix=suffix, number=g0 + 1)
+    return lines
+
+
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
                  B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None, maf=None, cs=False,
                  text_budget=TEXT_BUDGET, families=None, family_cover=80, consensus=None, consensus_budget=CONSENSUS_BUDGET,
-                 consensus_insertions=False):
+                 consensus_insertions=False, family_alignments=None, stack_budget=STACK_BUDGET):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
@@ -369,16 +420,24 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     without it): where most of the rows over a representative insert something in front of a column, the inserted bases are piled
     up and called too (--consensusInsertions; kernel K14, include/mimeo_hip.h "pileup v2, insertion columns") and go into the
     record, so that a private deletion of the representative does not become the family's; on rank 0, no collective; every other
-    output is unchanged."""
+    output is unchanged.  family_alignments (`mimeo self` only: ValueError with B): also write, to this file, one Stockholm 1.0
+    block per repeat family with the copies behind its consensus stacked in the representative's coordinates, the inserted
+    columns opened up (--familyAlignments; alignment_block, formats.stockholm_blocks, kernel K15, include/mimeo_hip.h "pileup v3,
+    the stack"): the families are those of `families` (family_cover applies; neither `families` nor `consensus` is needed), the
+    rows are fetched from the engine in runs of at most stack_budget bytes; on rank 0, no collective; with splitSelf the intra
+    block follows with F*_intra names; nothing is written when the TAB is recycled or a pair is listed twice; every other output
+    is unchanged."""
     dist = dist or Dist()
     cs = cs and paf is not None
     if families is not None and B is not None:
         raise ValueError('families needs a self job: the regions and the queries must lie in one genome')
     if consensus is not None and B is not None:
         raise ValueError('consensus needs a self job: the regions and the queries must lie in one genome')
+    if family_alignments is not None and B is not None:
+        raise ValueError('family_alignments needs a self job: the regions and the queries must lie in one genome')
     if consensus_insertions and consensus is None:
         raise ValueError('consensus_insertions needs consensus: there is no library to insert into')
-    if (families is not None or consensus is not None) and not 1 <= int(family_cover) <= 100:
+    if (families is not None or consensus is not None or family_alignments is not None) and not 1 <= int(family_cover) <= 100:
         raise ValueError('family_cover must be in 1..100, not %r' % (family_cover,))
     kept_paths = None
     outtab_intra = outtab + '_intra.tab'
@@ -386,9 +445,10 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     if not reuseTab or not os.path.isfile(outtab):
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
         blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist,
-                                               paths=paf is not None or region_stats is not None or maf is not None or families is not None or consensus is not None,
+                                               paths=paf is not None or region_stats is not None or maf is not None or families is not None or consensus is not None
+                                               or family_alignments is not None,
                                                divergence=divergence and paf is not None, paf_rows=paf is not None)
-        if region_stats is not None or families is not None or consensus is not None:
+        if region_stats is not None or families is not None or consensus is not None or family_alignments is not None:
             kept_paths = more[1]
         if paf is not None and dist.rank == 0:
             write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None, cs=(A, B, more[1], blocks, text_budget) if cs else None)
@@ -466,6 +526,20 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
                                       bool(consensus_insertions))
             with open(consensus, 'w') as f:
                 for line in cl:
+                    f.write(line + '\n')
+    if family_alignments is not None:
+        if kept_paths is None:
+            logging.warning('--familyAlignments needs the alignments\' paths: none with a recycled alignment file or a pair listed twice; %s is not written',
+                            family_alignments)
+        else:
+            none = np.zeros(0, dtype=engine._ffi.INTERVAL)
+            al = alignment_block(A, kept_paths, ~intra if splitSelf else np.ones(kept.shape[0], bool), reg_main[0] if reg_main else none, str(prefix),
+                                 int(family_cover), '', consensus_budget, stack_budget)
+            if splitSelf:   # the intra block's families follow, as in --families
+                al += alignment_block(A, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), int(family_cover), '_intra', consensus_budget,
+                                      stack_budget)
+            with open(family_alignments, 'w') as f:
+                for line in al:
                     f.write(line + '\n')
     return lines
 
