@@ -689,6 +689,72 @@ int mimeo_path_stack(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */,
                      uint64_t **row_first /* nitems + 1 */, uint8_t **rows /* row_first[nitems] bytes */);
 
 /*
+ * The rows of a pile against the call (kernel K16): how far every copy of a family is from the family's consensus — the number
+ * that dates a copy, and, binned and weighted by bases, the repeat landscape of a library.  mimeo_path_window_stats measures a
+ * row against the region's own copy, which between two copies is twice the distance to their ancestor and is wrong wherever
+ * the representative carries a private indel; mimeo_path_stack could hand the rows over as text, nitems * W bytes for six
+ * integers per item.  Here the aligned query strand is compared on the device with a supplied call instead of with the
+ * target's own base, inserted columns included.
+ *
+ * "Pileup v4, rows against the call".  Everything up to nsites is word for word the argument list of mimeo_path_stack, and the
+ * checks are the same, in the same order; `voters` of a site is not read.  `call` is indexed as mimeo_path_pileup returns it:
+ * column x of window g is call[col_first[g] + (x - start)]; `icall` as mimeo_path_insertions returns it: column j of site s is
+ * icall[icol_first[s] + j].  Every byte of both is one of A C G T N -.
+ *
+ * Item k = (aln, g, w0, w1), with b_k, p_k and dq_k as for mimeo_path_window_stats; as for mimeo_path_stack, lo = max of w0 and
+ * the first block's t, hi = min of w1 and the last block's end.  A record without a block, or lo >= hi, gives eight zeros.
+ *
+ * A pair (c, y) — c from the call, y from the aligned query strand, the N plane deciding first — is classified:
+ *   ambiguous       c or y is N;
+ *   matches         c == y;
+ *   transitions     A <-> G, C <-> T;
+ *   transversions   every other pair.
+ * Target columns, x in [lo, hi), c = call[col_first[g] + (x - start)]:
+ *   under block b_k, c a letter   classify (c, y), y the base at b_k.q + (x - b_k.t);
+ *   under a block, c == '-'       ins_bases += 1: the copy holds a base where the consensus has none;
+ *   in a gap [p_k, b_k.t), c a letter   del_bases += 1;
+ *   in a gap, c == '-'            nothing.
+ * Inserted runs, every k > 0 with dq_k > 0 and w0 <= p_k < w1 (the never-split rule), base j < dq_k, y the base at
+ * b_{k-1}.q + b_{k-1}.len + j:
+ *   a site s = (g, p_k) exists, j < ncols, and icall[icol_first[s] + j] is a letter   classify;
+ *   every other case              ins_bases += 1: no site, a run beyond ncols, or '-' in the consensus.
+ * Spanned sites, every site s of window g with w0 <= x_s < w1 and first block's t < x_s < last block's end:
+ *   every column j whose icall byte is a letter and for which the item has no j-th inserted base there   del_bases += 1.  It
+ *   has none where no block has p_k == x_s, where dq_k == 0, or where j >= dq_k; a site inside a deletion is included.
+ * q_lo and q_hi are the stretch of mimeo_stack_row: the item's bases under its target columns and in its runs.
+ *
+ * What a caller may rely on:
+ *   - matches + transitions + transversions + ambiguous + ins_bases == q_hi - q_lo;
+ *   - q_lo and q_hi are those of mimeo_path_stack for the same inputs;
+ *   - with `call` the target's own letters (mimeo_path_pileup without items) and nsites == 0, the first six fields of item k
+ *     equal matches, transitions, transversions, ambiguous, ins_bases, del_bases of mimeo_path_window_stats for that item alone
+ *     in a group, wherever the target's letter is not N; where it is N both count the column ambiguous;
+ *   - over a window's items, for every letter column of the call the classified letters number a + c + g + t + n of
+ *     mimeo_path_pileup at that column, and likewise those of mimeo_path_insertions at a site's letter columns;
+ *   - the counts are exact integers and depend on nothing but the sequences, blocks, windows, items, sites and the two calls:
+ *     not on slices, jobs, launches or the grid.
+ *
+ * Everything is checked on the host before anything is uploaded; a violation is MIMEO_ERR_ARG with a message that starts with
+ * "mimeo_path_call_stats:" and names the site, the item, the window, the record and the block, or — checked last — the column
+ * of `call` or the insertion column of `icall` whose byte is not one of the six.  call is NULL only where the windows have no
+ * column, icall iff nicols == 0.  nitems == 0 returns MIMEO_OK at once behind the checks; nsites == 0 is legal.  Records and
+ * blocks go to the device in the same bounded slices as for mimeo_path_stats, and only the slices that an item asks for; the
+ * two calls are packed into bit planes on the device once per call, 1.5 bytes of device memory per column while it runs.
+ *
+ * A new symbol beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs it checks for the symbol.
+ */
+typedef struct mimeo_call_stats {
+    uint32_t matches, transitions, transversions, ambiguous;
+    uint32_t ins_bases, del_bases, q_lo, q_hi;
+} mimeo_call_stats;                                            /* 32 bytes */
+int mimeo_path_call_stats(const mimeo_genome *T, const mimeo_genome *Q /* NULL: T */, const mimeo_alignment *aln, uint64_t n,
+                          const uint64_t *path_first, const mimeo_path_block *blocks, uint64_t nblocks,
+                          const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items, uint64_t nitems,
+                          const mimeo_insert_site *sites, uint64_t nsites,
+                          const uint8_t *call /* ncols bytes */, const uint8_t *icall /* nicols bytes, NULL iff nicols == 0 */,
+                          mimeo_call_stats *out /* caller's, nitems entries */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  A left-out pair is a scaffold pair: EVERY entry of the

@@ -123,6 +123,24 @@ def add_family_alignments(parser):
                              'a profile-HMM builder. Off by default. Nothing is written with --recycle when the alignment file exists.')
 
 
+def add_copy_divergence(parser):
+    """--copyDivergence and --landscape of `mimeo self` (`mimeo x` has its query in another genome)"""
+    parser.add_argument('--copyDivergence', type=str, default=None, metavar='FILE',
+                        help='Also write to FILE, tab-separated, one line per member of every repeat family (the families of --families; '
+                             '--familyCover applies; none of --families, --consensus, --familyAlignments need be given): the '
+                             'representative feature (role rep) and every copy that aligns to it (role copy; the sequence rows of '
+                             '--familyAlignments), with the copy\'s position, its columns against the family\'s consensus (that of '
+                             '--consensus --consensusInsertions) counted on the GPU - matches, transitions, transversions, ambiguous, '
+                             'ins_bases, del_bases - the divergence (ts + tv) / (m + ts + tv) and Kimura\'s two-parameter distance kd, '
+                             'which dates the copy. Off by default. Nothing is written with --recycle when the alignment file exists.')
+    parser.add_argument('--landscape', type=str, default=None, metavar='FILE',
+                        help='Also write the repeat landscape to FILE, tab-separated: per repeat family, and over all of them (family '
+                             '"all"), the members of --copyDivergence binned by their Kimura distance to the family\'s consensus in bins of '
+                             '0.01 up to 0.50 (then 0.50-inf, and NA for saturated copies), with the copies and the aligned bases in each '
+                             'non-empty bin. Works alone or with --copyDivergence, which shares its computation. Off by default. '
+                             'Nothing is written with --recycle when the alignment file exists.')
+
+
 def check_consensus(parser, args):
     """--consensusInsertions of `mimeo self` (parser.error exits with status 2, before the engine starts)"""
     if args.consensusInsertions and args.consensus is None:

@@ -20,7 +20,7 @@ SYMBOLS = [
     'mimeo_genome_keep_indexes', 'mimeo_genome_drop_indexes', 'mimeo_genome_build_indexes', 'mimeo_coverage_bedgraph',
     'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths', 'mimeo_path_stats',
     'mimeo_path_window_stats', 'mimeo_path_text', 'mimeo_link_regions', 'mimeo_path_pileup',
-    'mimeo_path_insertions', 'mimeo_path_stack',
+    'mimeo_path_insertions', 'mimeo_path_stack', 'mimeo_path_call_stats',
 ]
 
 
@@ -79,6 +79,8 @@ INSERT_RESULT = np.dtype([(n, '<u4') for n in ('runs', 'bases', 'longer', 'max_l
 INSERT_COLUMN = np.dtype([(n, '<u4') for n in ('a', 'c', 'g', 't', 'n')])   # mimeo_insert_column, 20 bytes
 INSERT_MAX_COLS = 1024   # insertion columns of one site, at most (include/mimeo_hip.h)
 STACK_ROW = np.dtype([(n, '<u4') for n in ('q_lo', 'q_hi', 'bases', 'hidden')])   # mimeo_stack_row, 16 bytes
+CALL_STATS = np.dtype([(n, '<u4') for n in ('matches', 'transitions', 'transversions', 'ambiguous', 'ins_bases', 'del_bases', 'q_lo',
+                                             'q_hi')])   # mimeo_call_stats, 32 bytes
 DEPTH_RUN = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4'), ('depth', '<u4')])
 
 _lib = None
@@ -138,6 +140,8 @@ def load():
         lib.mimeo_path_insertions.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp]
     if hasattr(lib, 'mimeo_path_stack'):
         lib.mimeo_path_stack.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(lib, 'mimeo_path_call_stats'):
+        lib.mimeo_path_call_stats.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

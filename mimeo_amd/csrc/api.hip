@@ -465,6 +465,18 @@ int mimeo_path_stack(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_a
     return path_stack_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, windows, nwin, items, nitems, sites, nsites, res, row_first, rows);
 }
 
+int mimeo_path_call_stats(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *path_first,
+                          const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
+                          uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, const uint8_t *call, const uint8_t *icall, mimeo_call_stats *out) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!T || (nitems && !out) || (nsites && !sites) || (nwin && !windows) || (nitems && !items) || (n && (!aln || !path_first)) || (nblocks && !blocks)) {
+        set_error("mimeo_path_call_stats: null argument");
+        return MIMEO_ERR_ARG;
+    }
+    return path_call_stats_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, windows, nwin, items, nitems, sites, nsites, call, icall, out);
+}
+
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {
     if (!n) { set_error("null argument"); return MIMEO_ERR_ARG; }
     const auto &f = failed_pairs();

@@ -388,5 +388,10 @@ int path_insertions_device(const mimeo_genome *T, const mimeo_genome *Q, const m
 int path_stack_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
                       const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
                       uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, mimeo_stack_row *res, uint64_t **row_first, uint8_t **rows);
+// K16: the six column counts and the query stretch of every item of a pileup against a supplied call (k16_call_stats.hip);
+// host in, host out.  Q is never null here.
+int path_call_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,
+                           const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
+                           uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, const uint8_t *call, const uint8_t *icall, mimeo_call_stats *out);
 
 }  // namespace mimeo

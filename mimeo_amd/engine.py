@@ -376,6 +376,49 @@ def stack(A, B, records, first, blocks, windows, items, sites):
     return res, row_first, _ffi.take(pr, C.c_uint64(int(row_first[-1])), np.dtype(np.uint8))
 
 
+def call_stats(A, B, records, first, blocks, windows, items, sites, call, icall):
+    """The rows of a pile against the call (mimeo_path_call_stats, kernel K16): one _ffi.CALL_STATS row per item — the columns of
+    the item's aligned query strand against `call`, the consensus byte per target column of the windows as pileup returns it, and
+    at the sites against `icall`, the byte per insertion column as insertions returns it: matches, transitions, transversions and
+    ambiguous columns, ins_bases (bases of the copy where the consensus has none), del_bases (letters of the consensus where the
+    copy has no base) and the stretch [q_lo, q_hi) of the aligned query strand that stack reports (include/mimeo_hip.h "pileup v4,
+    rows against the call" has the rules).  records / first / blocks / windows / items / sites exactly as for stack (voters is not
+    read; no site at all is legal, icall is then empty or None).  Every byte of call and icall is one of A C G T N -.  A bad
+    path, window, item, site or byte is a RuntimeError naming it, raised before anything runs on the device."""
+    recs, first, blk = _paths(records, first, blocks)
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_path_call_stats'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_path_call_stats: rebuild the library')
+    win = np.asarray(windows)
+    if win.dtype != _ffi.PILEUP_WINDOW:
+        a = np.asarray(win, dtype=np.uint32).reshape(-1, 3)
+        win = np.zeros(a.shape[0], dtype=_ffi.PILEUP_WINDOW)
+        win['tid'], win['start'], win['end'] = a[:, 0], a[:, 1], a[:, 2]
+    win = np.ascontiguousarray(win)
+    it = _window_items(items)
+    st = np.asarray(sites)
+    if st.dtype != _ffi.INSERT_SITE:
+        a = np.asarray(st, dtype=np.uint32).reshape(-1, 4)
+        st = np.zeros(a.shape[0], dtype=_ffi.INSERT_SITE)
+        st['window'], st['x'], st['ncols'], st['voters'] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    st = np.ascontiguousarray(st)
+    as_bytes = lambda b: np.zeros(0, dtype=np.uint8) if b is None else np.ascontiguousarray(np.frombuffer(b, dtype=np.uint8) if isinstance(b, (bytes, bytearray))
+                                                                                            else np.asarray(b, dtype=np.uint8))
+    cl, icl = as_bytes(call), as_bytes(icall)
+    # the library reads as many bytes as the windows and sites have columns: a shorter array never reaches it
+    ncols = int(np.maximum(win['end'].astype(np.int64) - win['start'].astype(np.int64), 0).sum())
+    nicols = int(np.minimum(st['ncols'].astype(np.int64), _ffi.INSERT_MAX_COLS).sum())
+    # (None is NULL to the library, which refuses it where there are columns)
+    if (call is not None and cl.size != ncols) or (icall is not None and icl.size != nicols):
+        raise ValueError('call_stats: call has %d bytes for %d columns, icall %d for %d insertion columns' % (cl.size, ncols, icl.size, nicols))
+    out = np.zeros(it.size, dtype=_ffi.CALL_STATS)
+    _ffi.check(lib.mimeo_path_call_stats(A._h, B._h if B is not None else None, recs.ctypes.data if recs.size else None, recs.size, first.ctypes.data,
+                                         blk.ctypes.data if blk.size else None, blk.size, win.ctypes.data if win.size else None, win.size,
+                                         it.ctypes.data if it.size else None, it.size, st.ctypes.data if st.size else None, st.size,
+                                         cl.ctypes.data if cl.size else None, icl.ctypes.data if icl.size else None, out.ctypes.data if it.size else None))
+    return out
+
+
 def path_text(A, B, records, first, blocks):
     """The text of alignment paths (mimeo_path_text, kernel K11): (row_first, trow, qrow) as numpy arrays (<u8, uint8, uint8).
     Row i is trow[row_first[i]:row_first[i + 1]] over the same range of qrow: the target's letters over the aligned query

@@ -3,6 +3,7 @@ lastz and bedtools calls.  Every function cites the reference command text it re
 relative to /root/reference/src/mimeo); the engine (HIP) supplies the numbers, these functions
 supply the bytes.
 """
+import bisect
 import math
 import os
 import re
@@ -635,6 +636,113 @@ def stockholm_blocks(regions, names_sorted, prefix, reps, sites, own, call, ical
         lines.append('#=GC cons ' + open_up(call[at:at + n], np.where(ins == ord('-'), ord('.'), ins).astype(np.uint8)))
         lines.append('//')
         at += n
+    return lines
+
+
+CALL_STATS = np.dtype([(n, '<u4') for n in ('matches', 'transitions', 'transversions', 'ambiguous', 'ins_bases', 'del_bases', 'q_lo',
+                                             'q_hi')])   # _ffi.CALL_STATS (this module does not load the library)
+COPY_DIVERGENCE_HEADER = '\t'.join(('#family', 'role', 'seqid', 'start', 'end', 'strand') + CALL_STATS.names[:6] + ('div', 'kd'))
+LANDSCAPE_HEADER = '\t'.join(('#family', 'kd_lo', 'kd_hi', 'copies', 'bases'))
+LANDSCAPE_BINS = 50   # bins of 0.01 from 0 up to 0.50; then one for everything from 0.50 on and one for the saturated copies
+_LANDSCAPE_EDGES = [k / 100 for k in range(LANDSCAPE_BINS + 1)]   # k / 100 is the double of the decimal: 0.07 falls into [0.07, 0.08)
+_CODE = np.full(256, 4, dtype=np.uint8)   # A C G T: 0 .. 3, a transition flips bit 1; everything else 4
+_CODE[list(b'ACGT')] = (0, 1, 2, 3)
+
+
+def own_call_stats(own, call, sites, icall, windows):
+    """The representative's own row of --copyDivergence for a run of windows, as engine.call_stats (kernel K16) would count a row
+    that lies under every target column and inserts nothing: one CALL_STATS row per window.  own: the representative's own
+    letters and call: the consensus byte per target column of the windows, one behind the other (engine.pileup without and with
+    items); sites / icall: the _ffi.INSERT_SITE rows of these windows and the consensus byte per insertion column.  Per target
+    column with c = call and y = own: c == '-' is an ins_bases; otherwise the pair is ambiguous where either is N, a match where
+    they are equal, a transition for A<->G and C<->T and a transversion otherwise.  Every letter column of the window's sites is a
+    del_bases.  [q_lo, q_hi) is the window itself."""
+    win = np.asarray(windows)
+    own, call, icall = (np.asarray(x, dtype=np.uint8) for x in (own, call, icall))
+    out = np.zeros(win.size, dtype=CALL_STATS)
+    icol_first = np.concatenate([[0], np.cumsum(sites['ncols'].astype(np.int64))]).astype(np.int64)
+    at = 0
+    for g in range(win.size):
+        n = int(win['end'][g]) - int(win['start'][g])
+        c, y = call[at:at + n], _CODE[own[at:at + n]]
+        at += n
+        letter = c != ord('-')
+        cc = _CODE[c]
+        amb = letter & ((cc == 4) | (y == 4))
+        d = cc ^ y
+        s0, s1 = (int(v) for v in np.searchsorted(sites['window'], [g, g + 1], side='left'))
+        out[g] = (int((letter & ~amb & (d == 0)).sum()), int((letter & ~amb & (d == 2)).sum()), int((letter & ~amb & (d != 0) & (d != 2)).sum()),
+                  int(amb.sum()), int((~letter).sum()), int((icall[int(icol_first[s0]):int(icol_first[s1])] != ord('-')).sum()),
+                  int(win['start'][g]), int(win['end'][g]))
+    return out
+
+
+def copy_stretch(qlen, qstrand, q_lo, q_hi):
+    """(start, end, strand) of a copy on its scaffold's plus strand, 0-based half-open, from the stretch [q_lo, q_hi) of the aligned
+    strand (engine.call_stats, engine.stack): the bases that stockholm_row_name names 1-based."""
+    return (qlen - q_hi, qlen - q_lo, '-') if qstrand else (q_lo, q_hi, '+')
+
+
+def _copy_values(s):
+    """(div, kd) of one CALL_STATS row: div = (ts + tv) / (m + ts + tv), None without an unambiguous column; kd = Kimura's
+    distance as divergence_values computes it, None where it is undefined."""
+    m, ts, tv = int(s['matches']), int(s['transitions']), int(s['transversions'])
+    kd = divergence_values({'matches': m, 'transitions': ts, 'transversions': tv, 'ambiguous': int(s['ambiguous']), 'ins_runs': 0, 'del_runs': 0})[3]
+    return ((ts + tv) / (m + ts + tv) if m + ts + tv else None), kd
+
+
+def copy_divergence_lines(members, header=True):
+    """--copyDivergence: one line per family member with bases — how far the copy is from its family's consensus.  members: per
+    line (family name, role 'rep' or 'copy', seqid, start, end, strand, a CALL_STATS row), in the order of the file
+    (workflow.divergence_block); start / end the copy's stretch on the plus strand, 0-based half-open.  The columns are
+    COPY_DIVERGENCE_HEADER's: the six counts of the row against the consensus (engine.call_stats, kernel K16; own_call_stats for
+    the representative), div = (transitions + transversions) / (matches + transitions + transversions) and kd = Kimura's
+    two-parameter distance over the same columns, both %.4f, NA where undefined (no unambiguous column; kd also where saturated)."""
+    lines = [COPY_DIVERGENCE_HEADER] if header else []
+    for family, role, seqid, start, end, strand, s in members:
+        div, kd = _copy_values(s)
+        lines.append('\t'.join([family, role, seqid, str(int(start)), str(int(end)), strand] + [str(int(s[f])) for f in CALL_STATS.names[:6]] +
+                               ['%.4f' % div if div is not None else 'NA', '%.4f' % kd if kd is not None else 'NA']))
+    return lines
+
+
+def landscape_bin(kd):
+    """The bin of a copy in the landscape: k for kd in [k / 100, (k + 1) / 100), k < 50; 50 from 0.50 on; 51 where kd is None."""
+    if kd is None:
+        return LANDSCAPE_BINS + 1
+    return min(bisect.bisect_right(_LANDSCAPE_EDGES, kd) - 1, LANDSCAPE_BINS)
+
+
+def landscape_lines(members, header=True, families=None):
+    """--landscape: the repeat landscape — per family the copies binned by their Kimura distance to the family's consensus and
+    weighted by bases.  members: as for copy_divergence_lines (the representative counts as a copy of its family); families: the
+    family names in the order of the file (None: in the order of their first member; a family without a member writes nothing).
+    Lines of LANDSCAPE_HEADER: kd_lo and kd_hi (%.2f) of a bin 0.01 wide from 0 up to 0.50, `0.50 inf` for everything beyond
+    and `NA NA` for the copies whose distance is undefined (saturated); copies, and bases = matches + transitions +
+    transversions + ambiguous of the copies in the bin.  Only non-empty bins are written, per family in order; the same over all
+    families follows under the name `all`."""
+    lines = [LANDSCAPE_HEADER] if header else []
+    if families is None:
+        families = list(dict.fromkeys(m[0] for m in members))
+    bins = {f: {} for f in families}
+    total = {}
+    for m in members:
+        s = m[6]
+        b = landscape_bin(_copy_values(s)[1])
+        bases = int(s['matches']) + int(s['transitions']) + int(s['transversions']) + int(s['ambiguous'])
+        for acc in (bins[m[0]], total):
+            c = acc.setdefault(b, [0, 0])
+            c[0] += 1
+            c[1] += bases
+
+    def rows(name, acc):
+        for b in sorted(acc):
+            lo, hi = ('NA', 'NA') if b > LANDSCAPE_BINS else ('0.50', 'inf') if b == LANDSCAPE_BINS else ('%.2f' % (b / 100), '%.2f' % ((b + 1) / 100))
+            yield '\t'.join([name, lo, hi, str(acc[b][0]), str(acc[b][1])])
+
+    for f in families:
+        lines.extend(rows(f, bins[f]))
+    lines.extend(rows('all', total))
     return lines
 
 

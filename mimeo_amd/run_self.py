@@ -16,6 +16,7 @@ def mainArgs(argv=None):
     _cli.add_families(parser)
     _cli.add_consensus(parser)
     _cli.add_family_alignments(parser)
+    _cli.add_copy_divergence(parser)
     parser.add_argument('--minCov', type=int, default=3, help='Minimum depth of aligned segments to report repeat feature.')
     parser.add_argument('--intraCov', type=int, default=5,
                         help='Minimum depth of aligned segments from same scaffold to report feature. Used if "--strictSelf" mode is selected.')
@@ -40,7 +41,8 @@ def main(argv=None):
                           label=args.label, prefix=args.prefix, dist=dist,
                           anchor_rule=args.anchorRule, bound_extensions=args.boundExtensions, paf=args.paf, divergence=args.divergence,
                           region_stats=args.regionStats, maf=args.maf, cs=args.cs, families=args.families, family_cover=args.familyCover,
-                          consensus=args.consensus, consensus_insertions=args.consensusInsertions, family_alignments=args.familyAlignments)
+                          consensus=args.consensus, consensus_insertions=args.consensusInsertions, family_alignments=args.familyAlignments,
+                          copy_divergence=args.copyDivergence, landscape=args.landscape)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

@@ -349,6 +349,23 @@ def consensus_block(A, kept_paths, select, regions, prefix, cover, suffix, budge
 STACK_BUDGET = 1 << 26   # row bytes asked of engine.stack at once (one row goes whatever its size)
 
 
+def pile_calls(A, recs, f2, b2, win, run):
+    """What --familyAlignments and --copyDivergence / --landscape share for one run of windows `win` with the items `run` over
+    them: engine.pileup (kernel K13) for the counts and the call, and once more without items for the representative's own
+    letters; the sites (formats.stack_sites: every column in front of which a row inserts something, with as many columns as its
+    longest run, which a first engine.insertions call over the sites reports); engine.insertions (kernel K14) for the call of the
+    insertion columns.  Returns (own, call, sites, icall)."""
+    cols, call = engine.pileup(A, None, recs, f2, b2, win, run)
+    _, own = engine.pileup(A, None, recs, f2, b2, win, run[:0], counts=False)
+    sites = formats.stack_sites(win, cols)
+    icall = np.zeros(0, dtype=np.uint8)
+    if sites.size:
+        res, _, _ = engine.insertions(A, None, recs, f2, b2, win, run, sites, counts=False, call=False)
+        sites = formats.stack_sites(win, cols, max_len=res['max_len'])
+        _, _, icall = engine.insertions(A, None, recs, f2, b2, win, run, sites, results=False, counts=False)
+    return own, call, sites, icall
+
+
 def alignment_block(A, kept_paths, select, regions, prefix, cover, suffix, budget=CONSENSUS_BUDGET, stack_budget=STACK_BUDGET):
     """--familyAlignments for one block of GFF3 rows: the families, representatives, windows and piles of consensus_block
     (family_piles), and per run of windows of at most `budget` columns: engine.pileup (kernel K13) for the counts and the call,
@@ -364,14 +381,7 @@ def alignment_block(A, kept_paths, select, regions, prefix, cover, suffix, budge
         win = windows[g0:g1]
         run = its[np.searchsorted(its['group'], g0, side='left'):np.searchsorted(its['group'], g1, side='left')].copy()
         run['group'] -= g0
-        cols, call = engine.pileup(A, None, recs, f2, b2, win, run)
-        _, own = engine.pileup(A, None, recs, f2, b2, win, run[:0], counts=False)
-        sites = formats.stack_sites(win, cols)
-        icall = np.zeros(0, dtype=np.uint8)
-        if sites.size:
-            res, _, _ = engine.insertions(A, None, recs, f2, b2, win, run, sites, counts=False, call=False)
-            sites = formats.stack_sites(win, cols, max_len=res['max_len'])
-            _, _, icall = engine.insertions(A, None, recs, f2, b2, win, run, sites, results=False, counts=False)
+        own, call, sites, icall = pile_calls(A, recs, f2, b2, win, run)
         width = (win['end'].astype(np.int64) - win['start']) + np.bincount(sites['window'], weights=sites['ncols'], minlength=g1 - g0).astype(np.int64)
         rows = []
         for i0, i1 in text_runs(width[run['group'].astype(np.int64)] if run.size else np.zeros(0, dtype=np.int64), stack_budget):
@@ -388,11 +398,42 @@ def alignment_block(A, kept_paths, select, regions, prefix, cover, suffix, budge
     return lines
 
 
+def divergence_block(A, kept_paths, select, regions, prefix, cover, suffix, budget=CONSENSUS_BUDGET):
+    """--copyDivergence and --landscape for one block of GFF3 rows: the families, representatives, windows and piles of
+    consensus_block (family_piles), and per run of windows of at most `budget` columns the consensus exactly as alignment_block
+    makes it (pile_calls: the call of every target column and of the insertion columns of every site), then one
+    engine.call_stats call (kernel K16) over the run's items: every row of the pile against the consensus.  Returns the members
+    of formats.copy_divergence_lines and formats.landscape_lines: per family the representative's own row
+    (formats.own_call_stats) and one per item with bases, in the order of the items — the sequence rows of the family's
+    Stockholm block.  They do not depend on the budget."""
+    (recs, f2, b2), names_sorted, reps, windows, its = family_piles(A, kept_paths, select, regions, cover)
+    members = []
+    for g0, g1 in text_runs(windows['end'].astype(np.int64) - windows['start'], budget):
+        win = windows[g0:g1]
+        run = its[np.searchsorted(its['group'], g0, side='left'):np.searchsorted(its['group'], g1, side='left')].copy()
+        run['group'] -= g0
+        own, call, sites, icall = pile_calls(A, recs, f2, b2, win, run)
+        stats = engine.call_stats(A, None, recs, f2, b2, win, run, sites, call, icall)
+        mine = formats.own_call_stats(own, call, sites, icall, win)
+        at = 0
+        for g in range(g1 - g0):
+            r = regions[reps[g0 + g][0]]
+            family = 'F%d%s' % (g0 + g + 1, suffix)
+            members.append((family, 'rep', names_sorted[int(r['chrom'])], int(r['start']), int(r['end']), '+', mine[g]))
+            while at < run.size and int(run['group'][at]) == g:   # the items are sorted by window
+                s, a = stats[at], int(run['aln'][at])
+                at += 1
+                if s['q_hi'] > s['q_lo']:
+                    qid = int(recs['qid'][a])
+                    members.append((family, 'copy', A.names[qid]) + formats.copy_stretch(int(A.lengths[qid]), int(recs['qstrand'][a]), int(s['q_lo']), int(s['q_hi'])) + (s,))
+    return members
+
+
 def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000, minCov=3, intraCov=5,
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
                  B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None, maf=None, cs=False,
                  text_budget=TEXT_BUDGET, families=None, family_cover=80, consensus=None, consensus_budget=CONSENSUS_BUDGET,
-                 consensus_insertions=False, family_alignments=None, stack_budget=STACK_BUDGET):
+                 consensus_insertions=False, family_alignments=None, stack_budget=STACK_BUDGET, copy_divergence=None, landscape=None):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
@@ -426,7 +467,13 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     the stack"): the families are those of `families` (family_cover applies; neither `families` nor `consensus` is needed), the
     rows are fetched from the engine in runs of at most stack_budget bytes; on rank 0, no collective; with splitSelf the intra
     block follows with F*_intra names; nothing is written when the TAB is recycled or a pair is listed twice; every other output
-    is unchanged."""
+    is unchanged.  copy_divergence / landscape (`mimeo self` only: ValueError with B): also write, to these files, one line per
+    family member with its column counts, divergence and Kimura distance against the family's consensus (--copyDivergence;
+    formats.copy_divergence_lines) and the members binned by that distance and weighted by bases (--landscape;
+    formats.landscape_lines): divergence_block, kernel K16, include/mimeo_hip.h "pileup v4, rows against the call".  The families
+    are those of `families` (family_cover applies; none of `families`, `consensus`, `family_alignments` is needed); either works
+    alone, and both share one computation; on rank 0, no collective; with splitSelf the intra block follows with F*_intra
+    names; nothing is written when the TAB is recycled or a pair is listed twice; every other output is unchanged."""
     dist = dist or Dist()
     cs = cs and paf is not None
     if families is not None and B is not None:
@@ -435,9 +482,14 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
         raise ValueError('consensus needs a self job: the regions and the queries must lie in one genome')
     if family_alignments is not None and B is not None:
         raise ValueError('family_alignments needs a self job: the regions and the queries must lie in one genome')
+    if copy_divergence is not None and B is not None:
+        raise ValueError('copy_divergence needs a self job: the regions and the queries must lie in one genome')
+    if landscape is not None and B is not None:
+        raise ValueError('landscape needs a self job: the regions and the queries must lie in one genome')
     if consensus_insertions and consensus is None:
         raise ValueError('consensus_insertions needs consensus: there is no library to insert into')
-    if (families is not None or consensus is not None or family_alignments is not None) and not 1 <= int(family_cover) <= 100:
+    if (families is not None or consensus is not None or family_alignments is not None or copy_divergence is not None or landscape is not None) and \
+            not 1 <= int(family_cover) <= 100:
         raise ValueError('family_cover must be in 1..100, not %r' % (family_cover,))
     kept_paths = None
     outtab_intra = outtab + '_intra.tab'
@@ -446,9 +498,10 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
         params = gapped_params(hspthresh, anchor_rule, bound_extensions)
         blocks, _, kept, *more = align_blocks(A, B, pairs, params, minLen, minIdt, dist,
                                                paths=paf is not None or region_stats is not None or maf is not None or families is not None or consensus is not None
-                                               or family_alignments is not None,
+                                               or family_alignments is not None or copy_divergence is not None or landscape is not None,
                                                divergence=divergence and paf is not None, paf_rows=paf is not None)
-        if region_stats is not None or families is not None or consensus is not None or family_alignments is not None:
+        if region_stats is not None or families is not None or consensus is not None or family_alignments is not None or copy_divergence is not None or \
+                landscape is not None:
             kept_paths = more[1]
         if paf is not None and dist.rank == 0:
             write_paf(paf, pairs, more[0], splitSelf=splitSelf and B is None, cs=(A, B, more[1], blocks, text_budget) if cs else None)
@@ -541,6 +594,23 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
             with open(family_alignments, 'w') as f:
                 for line in al:
                     f.write(line + '\n')
+    if copy_divergence is not None or landscape is not None:
+        flags = [(copy_divergence, '--copyDivergence', formats.copy_divergence_lines), (landscape, '--landscape', formats.landscape_lines)]
+        if kept_paths is None:
+            for path, flag, _ in flags:
+                if path is not None:
+                    logging.warning('%s needs the alignments\' paths: none with a recycled alignment file or a pair listed twice; %s is not written', flag, path)
+        else:
+            none = np.zeros(0, dtype=engine._ffi.INTERVAL)
+            members = divergence_block(A, kept_paths, ~intra if splitSelf else np.ones(kept.shape[0], bool), reg_main[0] if reg_main else none, str(prefix),
+                                       int(family_cover), '', consensus_budget)
+            if splitSelf:   # the intra block's families follow, as in --families
+                members += divergence_block(A, kept_paths, intra, reg_intra[0] if reg_intra else none, str(prefix), int(family_cover), '_intra', consensus_budget)
+            for path, _, make in flags:   # one computation for both files
+                if path is not None:
+                    with open(path, 'w') as f:
+                        for line in make(members):
+                            f.write(line + '\n')
     return lines
 
 
