@@ -755,6 +755,66 @@ int mimeo_path_call_stats(const mimeo_genome *T, const mimeo_genome *Q /* NULL: 
                           mimeo_call_stats *out /* caller's, nitems entries */);
 
 /*
+ * Terminal repeats of features (kernel K17): what kind of element a region is, read off its own two ends.  Two direct repeats
+ * at the ends are the LTRs of a retrotransposon, and their divergence dates that one insertion; two inverted repeats are the
+ * TIRs of a DNA transposon.  The seeded pipeline cannot see either (a TIR is 10 - 50 bases; a 12of19 seed and hspthresh 3000
+ * need about 33 clean ones), so this is a dense, exhaustive DP: for every item the first w bases against the last w bases,
+ * and against the reverse complement of the last w bases.  The result is the library's own currency — records and gap-free
+ * blocks as mimeo_align_units_paths returns them — so mimeo_path_stats, mimeo_path_text and the writers of CIGARs serve it.
+ *
+ * Item k = [start, end) on scaffold `chrom` of G, of length len; fwd and rc are the scaffold's forward strand and its stored
+ * reverse complement.
+ *   window     w = min(window, (end - start) / 2), integer division: the two windows never overlap
+ *   head       a[i] = fwd[start + i], 0 <= i < w
+ *   direct     out[2k], qstrand 0:      b[j] = fwd[end - w + j]
+ *   inverted   out[2k + 1], qstrand 1:  b[j] = rc[len - end + j] — the stored reverse complement; nothing is flipped, as in
+ *              the coordinates of mimeo_path_block
+ *   column     s(x, y) = +match where both bases are ACGT and equal, else -mismatch (the N plane decides first)
+ * A Gotoh local alignment over the cells (i, j), 0 <= i, j < w, with H = 0 (and no E, no F) outside:
+ *   E[i][j] = max(H[i][j-1] - gap_open - gap_extend, E[i][j-1] - gap_extend)    consumes b[j]: q jumps, an insertion
+ *   F[i][j] = max(H[i-1][j] - gap_open - gap_extend, F[i-1][j] - gap_extend)    consumes a[i]: t jumps, a deletion
+ *   H[i][j] = max(0, H[i-1][j-1] + s(a[i], b[j]), E[i][j], F[i][j])
+ * The best cell is the largest H; of equal cells the smallest i, then the smallest j.  Below min_score nothing is found.
+ * The traceback from the best cell decides every tie:
+ *   in H with value v > 0   the diagonal if v == H[i-1][j-1] + s; else to E if v == E[i][j]; else to F;
+ *   in E                    the gap was opened here — back to H at (i, j-1) — if E[i][j] == H[i][j-1] - gap_open - gap_extend,
+ *                           else it extends: E at (i, j-1);
+ *   in F                    the same with i - 1;
+ *   it stops where the H value reached is 0.
+ * The diagonal steps merge into blocks with t = start + i on the plus strand and q on the strand that was aligned: end - w + j
+ * (direct) or len - end + j (inverted); the path keeps the contract of mimeo_path_block.  The record: tid = qid = chrom;
+ * tstart / tend from the first and the last block; qstart / qend on the plus strand (qstrand 1: by the formula above); score
+ * the best H; id_d the sum of the blocks' len; id_n the matching columns — so what mimeo_path_stats promises for paths of
+ * mimeo_align_units_paths holds here too.  Nothing found (also w == 0): the record is zero except tid, qid and qstrand, and
+ * its path is empty; mimeo_path_stats accepts it and counts nothing.
+ *
+ * `out` is the caller's, 2 n records; *path_first (2 n + 1 entries), *blocks and *nblocks are the library's, released with
+ * mimeo_free (*blocks is NULL where there is no block).  Everything is checked before the device sees it: a window outside
+ * 1 .. 4096 is MIMEO_ERR_LIMIT; every other parameter out of range, a reserved field that is not 0, a chrom outside the
+ * genome or an item that is not start <= end <= len is MIMEO_ERR_ARG, with a message that starts with
+ * "mimeo_terminal_repeats:" and names the item.  n == 0 returns MIMEO_OK at once (path_first holds one zero).  The results
+ * are exact integers and depend on nothing but the sequence, the items and the parameters: not on how the jobs are cut into
+ * launches (the traceback of a job takes about w * w / 2 bytes of device memory while it runs, and a call takes a bounded
+ * share of what is free).
+ *
+ * Two new symbols beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs them checks for the symbols.
+ */
+typedef struct mimeo_terminal_params {
+    int32_t window;      /* bases of each end that are examined [1024]; 1 .. 4096, MIMEO_ERR_LIMIT outside   */
+    int32_t match;       /* [2]  1 .. 1000                                                                  */
+    int32_t mismatch;    /* [3]  penalty, 1 .. 1000; also every column with a non-ACGT base                  */
+    int32_t gap_open;    /* [5]  0 .. 1000; a gap of k bases costs gap_open + k * gap_extend (as lastz's)    */
+    int32_t gap_extend;  /* [2]  1 .. 1000                                                                  */
+    int32_t min_score;   /* [40] >= 1: an orientation whose best score is below it reports nothing          */
+    int32_t reserved[2]; /* must be 0 */
+} mimeo_terminal_params;
+int mimeo_terminal_params_default(mimeo_terminal_params *p);
+int mimeo_terminal_repeats(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n,
+                           const mimeo_terminal_params *p,
+                           mimeo_alignment *out /* caller's, 2 n entries */,
+                           uint64_t **path_first /* 2 n + 1 */, mimeo_path_block **blocks, uint64_t *nblocks);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  A left-out pair is a scaffold pair: EVERY entry of the

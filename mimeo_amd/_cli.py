@@ -141,6 +141,32 @@ def add_copy_divergence(parser):
                              'Nothing is written with --recycle when the alignment file exists.')
 
 
+def add_terminal_repeats(parser):
+    """--terminalRepeats, --terminalWindow and --terminalMinScore of `mimeo self` (the features of `mimeo x` lie in another genome)"""
+    parser.add_argument('--terminalRepeats', type=str, default=None, metavar='FILE',
+                        help='Also write to FILE, tab-separated, the repeats at the two ends of every feature of the GFF3: its first '
+                             '--terminalWindow bases against its last, as they are (kind LTR: a direct repeat, the long terminal repeats of '
+                             'a retrotransposon; kd between the two dates the insertion) and against their reverse complement (kind TIR: '
+                             'the terminal inverted repeats of a DNA transposon). An exhaustive affine-gap local alignment on the GPU '
+                             '(match 2, mismatch 3, gap open 5, gap extend 2), with no seed and none of --minIdt / --minLen, so a TIR of 20 '
+                             'bases is found. One line per orientation found: position of both repeats, score, columns, matches, '
+                             'transitions, transversions, gaps, identity, kd. Needs none of --paf, --families, --consensus. Off by default.')
+    parser.add_argument('--terminalWindow', type=int, default=1024, metavar='N',
+                        help='Bases of each end of a feature that --terminalRepeats examines, at most half the feature (1..4096). Default: 1024')
+    parser.add_argument('--terminalMinScore', type=int, default=40, metavar='S',
+                        help='Lowest score that --terminalRepeats reports. Two random 1024-base windows reached 19..25 (12 draws; 13..23 at '
+                             '256 bases, 40 draws), so the default keeps chance out while a perfect 20-base repeat (score 40) passes. Default: 40')
+
+
+def check_terminal(parser, args):
+    """the ranges of --terminalWindow and --terminalMinScore (parser.error exits with status 2, before the engine starts)"""
+    if not 1 <= args.terminalWindow <= 4096:
+        parser.error('--terminalWindow must be in 1..4096')
+    if args.terminalMinScore < 1:
+        parser.error('--terminalMinScore must be at least 1')
+    return args
+
+
 def check_consensus(parser, args):
     """--consensusInsertions of `mimeo self` (parser.error exits with status 2, before the engine starts)"""
     if args.consensusInsertions and args.consensus is None:

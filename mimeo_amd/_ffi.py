@@ -20,7 +20,8 @@ SYMBOLS = [
     'mimeo_genome_keep_indexes', 'mimeo_genome_drop_indexes', 'mimeo_genome_build_indexes', 'mimeo_coverage_bedgraph',
     'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths', 'mimeo_path_stats',
     'mimeo_path_window_stats', 'mimeo_path_text', 'mimeo_link_regions', 'mimeo_path_pileup',
-    'mimeo_path_insertions', 'mimeo_path_stack', 'mimeo_path_call_stats',
+    'mimeo_path_insertions', 'mimeo_path_stack', 'mimeo_path_call_stats', 'mimeo_terminal_params_default',
+    'mimeo_terminal_repeats',
 ]
 
 
@@ -43,6 +44,11 @@ class Params(C.Structure):
         d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n != 'reserved'}
         d['bound_extensions'] = self.bound_extensions
         return d
+
+
+class TerminalParams(C.Structure):   # mimeo_terminal_params, 32 bytes
+    _fields_ = [(n, C.c_int32) for n in ('window', 'match', 'mismatch', 'gap_open', 'gap_extend', 'min_score')] + [('reserved', C.c_int32 * 2)]
+    NAMES = ('window', 'match', 'mismatch', 'gap_open', 'gap_extend', 'min_score')
 
 
 ANCHOR_BOX, ANCHOR_PATH = 0, 1   # Params.anchor_rule (MIMEO_ANCHOR_*)
@@ -142,6 +148,9 @@ def load():
         lib.mimeo_path_stack.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(vp), C.POINTER(vp)]
     if hasattr(lib, 'mimeo_path_call_stats'):
         lib.mimeo_path_call_stats.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp]
+    if hasattr(lib, 'mimeo_terminal_repeats'):
+        lib.mimeo_terminal_params_default.argtypes = [C.POINTER(TerminalParams)]
+        lib.mimeo_terminal_repeats.argtypes = [vp, vp, u64, C.POINTER(TerminalParams), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

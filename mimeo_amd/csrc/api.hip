@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "terminal_host.h"
 
 namespace mimeo {
 
@@ -475,6 +476,23 @@ int mimeo_path_call_stats(const mimeo_genome *T, const mimeo_genome *Q, const mi
         return MIMEO_ERR_ARG;
     }
     return path_call_stats_device(T, Q ? Q : T, aln, n, path_first, blocks, nblocks, windows, nwin, items, nitems, sites, nsites, call, icall, out);
+}
+
+int mimeo_terminal_params_default(mimeo_terminal_params *p) {
+    if (!p) { set_error("mimeo_terminal_params_default: null argument"); return MIMEO_ERR_ARG; }
+    terminal_host::defaults(p);
+    return MIMEO_OK;
+}
+
+int mimeo_terminal_repeats(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n, const mimeo_terminal_params *p, mimeo_alignment *out,
+                           uint64_t **path_first, mimeo_path_block **blocks, uint64_t *nblocks) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!G || !p || !path_first || !blocks || !nblocks || (n && (!iv || !out))) {
+        set_error("mimeo_terminal_repeats: null argument");
+        return MIMEO_ERR_ARG;
+    }
+    return terminal_repeats_device(G, iv, n, p, out, path_first, blocks, nblocks);
 }
 
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {

@@ -394,4 +394,8 @@ int path_call_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const m
                            const mimeo_path_block *blocks, uint64_t nblocks, const mimeo_pileup_window *windows, uint64_t nwin, const mimeo_window_item *items,
                            uint64_t nitems, const mimeo_insert_site *sites, uint64_t nsites, const uint8_t *call, const uint8_t *icall, mimeo_call_stats *out);
 
+// K17: terminal repeats of features, both orientations of every item (k17_terminal.hip); host in, records into the caller's
+// `out`, two malloc'ed arrays out.
+int terminal_repeats_device(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n, const mimeo_terminal_params *p, mimeo_alignment *out,
+                            uint64_t **path_first, mimeo_path_block **blocks, uint64_t *nblocks);
 }  // namespace mimeo

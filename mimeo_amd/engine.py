@@ -437,6 +437,37 @@ def path_text(A, B, records, first, blocks):
     return row_first, _ffi.take(pt, total, np.dtype(np.uint8)), _ffi.take(pq, total, np.dtype(np.uint8))
 
 
+def terminal_repeats(A, intervals, **params):
+    """Terminal repeats of features (mimeo_terminal_repeats, kernel K17): for every (scaffold id, start, end) of genome A a full
+    affine-gap local alignment of its first w bases against its last w bases (record 2k, qstrand 0: a direct repeat, the LTRs of a
+    retrotransposon) and against the reverse complement of the last w bases (record 2k + 1, qstrand 1: an inverted repeat, the
+    TIRs of a DNA transposon), w = min(window, length // 2).  Returns (records[2n], first[2n + 1], blocks) in the dtypes of
+    align_pairs(..., paths=True), so path_stats, path_text and formats.cigar take them as they are; an orientation that scores
+    below min_score is a record of zeros (but tid, qid, qstrand) with an empty path.  params: window (1024; 1 .. 4096), match (2),
+    mismatch (3), gap_open (5), gap_extend (2), min_score (40) — include/mimeo_hip.h has the rules, ties included.  A bad
+    parameter or item is a RuntimeError naming it, raised before anything runs on the device."""
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_terminal_repeats'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_terminal_repeats: rebuild the library')
+    P = _ffi.TerminalParams()
+    _ffi.check(lib.mimeo_terminal_params_default(C.byref(P)))
+    for k, v in params.items():
+        if k not in _ffi.TerminalParams.NAMES:
+            raise TypeError('unknown terminal-repeat parameter %r' % k)
+        setattr(P, k, int(v))
+    iv = np.asarray(intervals)
+    if iv.dtype != _ffi.INTERVAL:
+        a = np.asarray(iv, dtype=np.uint32).reshape(-1, 3)
+        iv = np.zeros(a.shape[0], dtype=_ffi.INTERVAL)
+        iv['chrom'], iv['start'], iv['end'] = a[:, 0], a[:, 1], a[:, 2]
+    iv = np.ascontiguousarray(iv)
+    recs = np.zeros(2 * iv.size, dtype=_ffi.ALIGNMENT)
+    pf, pb, nb = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _ffi.check(lib.mimeo_terminal_repeats(A._h, iv.ctypes.data if iv.size else None, iv.size, C.byref(P), recs.ctypes.data if iv.size else None,
+                                          C.byref(pf), C.byref(pb), C.byref(nb)))
+    return recs, _ffi.take(pf, C.c_uint64(2 * iv.size + 1), np.dtype('<u8')), _ffi.take(pb, nb, _ffi.PATH_BLOCK)
+
+
 def failed_pairs():
     """Pairs of the last align_pairs / align_units call that hit a documented limit and were left out (the reference's script
     loses only the failing lastz run's rows: utils.py:125-128): [(index into the call's pair list, error code)]."""

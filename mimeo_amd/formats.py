@@ -434,6 +434,37 @@ def region_stat_lines(regions, names_sorted, prefix, stats, rows, header=True):
     return lines
 
 
+TERMINAL_REPEATS_HEADER = '\t'.join(('#feature', 'seqid', 'start', 'end', 'kind', 'window', 'left_start', 'left_end', 'right_start', 'right_end', 'score',
+                                     'columns', 'matches', 'ts', 'tv', 'ambiguous', 'gap_runs', 'gap_bases', 'identity', 'kd'))
+TERMINAL_KINDS = ('LTR', 'TIR')   # by qstrand: a direct repeat, an inverted repeat
+
+
+def terminal_repeat_lines(regions, names_sorted, prefix, window, records, stats, header=True):
+    """--terminalRepeats: TERMINAL_REPEATS_HEADER (header=True), then one tab-separated line per orientation that was found, so
+    0, 1 or 2 lines per region.  ID, seqid, start and end are those of the region's GFF3 row, as in region_stat_lines; records:
+    the 2 n records of engine.terminal_repeats for the regions (2 k direct: kind LTR; 2 k + 1 inverted: kind TIR); stats: their
+    rows of engine.path_stats.  window: the bases of each end that were examined, min(window, length // 2); left_* / right_*:
+    the two repeats on the plus strand, in the region's own convention (tstart / tend and qstart / qend of the record); columns
+    = matches + ts + tv + ambiguous; gap_runs / gap_bases: insertions and deletions together; identity = matches / columns and
+    kd (Kimura's two-parameter distance between the two repeats, which dates the insertion of an LTR element) as in
+    region_stat_lines, '.' where undefined."""
+    lines = [TERMINAL_REPEATS_HEADER] if header else []
+    for i, r in enumerate(regions, 1):
+        w = min(int(window), (int(r['end']) - int(r['start'])) // 2)
+        for o in (0, 1):
+            a, s = records[2 * (i - 1) + o], stats[2 * (i - 1) + o]
+            if int(a['id_d']) == 0:
+                continue   # nothing found in this orientation
+            c = [int(s[f]) for f in ('matches', 'transitions', 'transversions', 'ambiguous')]
+            columns = sum(c)
+            _, runs, _, kd = divergence_values(s)
+            lines.append('\t'.join(['%s_%05d' % (prefix, i), names_sorted[int(r['chrom'])], str(int(r['start'])), str(int(r['end'])), TERMINAL_KINDS[o], str(w),
+                                    str(int(a['tstart'])), str(int(a['tend'])), str(int(a['qstart'])), str(int(a['qend'])), str(int(a['score'])), str(columns)] +
+                                   [str(v) for v in c] + [str(runs), str(int(s['ins_bases']) + int(s['del_bases'])),
+                                                          '%.4f' % (c[0] / columns) if columns else '.', '%.4f' % kd if kd is not None else '.']))
+    return lines
+
+
 FAMILY_HEADER = '\t'.join(('#ID', 'seqid', 'start', 'end', 'family', 'members', 'family_bases', 'links'))
 
 

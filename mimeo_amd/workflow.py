@@ -268,6 +268,21 @@ def region_stat_block(A, B, kept_paths, select, regions, prefix, header):
     return formats.region_stat_lines(regions, names_sorted, prefix, stats, per_region, header=header)
 
 
+def terminal_block(A, regions, prefix, window, min_score, header):
+    """--terminalRepeats for one block of GFF3 rows: the regions as intervals of their scaffolds, one engine.terminal_repeats
+    call (kernel K17: each region's head against its tail, direct and inverted), one engine.path_stats call (K9) over the
+    returned records, the lines of formats.terminal_repeat_lines.  Needs no alignment of the job: only the regions."""
+    names_sorted = sorted(A.names, key=lambda s: s.encode())
+    tid = {n: i for i, n in enumerate(A.names)}
+    iv = np.zeros(len(regions), dtype=engine._ffi.INTERVAL)
+    if len(regions):
+        iv['chrom'] = [tid[names_sorted[int(c)]] for c in regions['chrom']]
+        iv['start'], iv['end'] = regions['start'], regions['end']
+    recs, first, blk = engine.terminal_repeats(A, iv, window=int(window), min_score=int(min_score))
+    stats = engine.path_stats(A, None, recs, first, blk)
+    return formats.terminal_repeat_lines(regions, names_sorted, prefix, window, recs, stats, header=header)
+
+
 def family_block(A, kept_paths, select, regions, prefix, cover, suffix, header):
     """--families for one block of GFF3 rows: the rows `select` (a mask) of the kept rows' (records, first, blocks) joined with
     `regions` (formats.region_items, without the trivial self rows), one engine.link_regions call (kernel K12), the lines of
@@ -433,7 +448,8 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
                  splitSelf=False, reuseTab=False, label='Self_repeats', prefix=None, dist=None, source='mimeo-self',
                  B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None, maf=None, cs=False,
                  text_budget=TEXT_BUDGET, families=None, family_cover=80, consensus=None, consensus_budget=CONSENSUS_BUDGET,
-                 consensus_insertions=False, family_alignments=None, stack_budget=STACK_BUDGET, copy_divergence=None, landscape=None):
+                 consensus_insertions=False, family_alignments=None, stack_budget=STACK_BUDGET, copy_divergence=None, landscape=None,
+                 terminal_repeats=None, terminal_window=1024, terminal_min_score=40):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
@@ -473,7 +489,13 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     formats.landscape_lines): divergence_block, kernel K16, include/mimeo_hip.h "pileup v4, rows against the call".  The families
     are those of `families` (family_cover applies; none of `families`, `consensus`, `family_alignments` is needed); either works
     alone, and both share one computation; on rank 0, no collective; with splitSelf the intra block follows with F*_intra
-    names; nothing is written when the TAB is recycled or a pair is listed twice; every other output is unchanged."""
+    names; nothing is written when the TAB is recycled or a pair is listed twice; every other output is unchanged.
+    terminal_repeats (`mimeo self` only: ValueError with B): also write, to this file, for every GFF3 row the repeats at its own
+    two ends (--terminalRepeats; terminal_block, formats.terminal_repeat_lines, kernel K17, include/mimeo_hip.h "Terminal repeats
+    of features"): the first terminal_window bases of the region against its last, direct (kind LTR) and inverted (kind TIR), a
+    full affine-gap local alignment each, reported from a score of terminal_min_score on.  It needs the regions alone — none of
+    paf, families or consensus, no paths, and it works with a recycled TAB; on rank 0, no collective; with splitSelf the intra
+    block's lines follow; every other output is unchanged."""
     dist = dist or Dist()
     cs = cs and paf is not None
     if families is not None and B is not None:
@@ -486,6 +508,13 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
         raise ValueError('copy_divergence needs a self job: the regions and the queries must lie in one genome')
     if landscape is not None and B is not None:
         raise ValueError('landscape needs a self job: the regions and the queries must lie in one genome')
+    if terminal_repeats is not None:
+        if B is not None:
+            raise ValueError('terminal_repeats needs a self job: the regions must lie in the genome that was aligned to itself')
+        if not 1 <= int(terminal_window) <= 4096:
+            raise ValueError('terminal_window must be in 1..4096, not %r' % (terminal_window,))
+        if int(terminal_min_score) < 1:
+            raise ValueError('terminal_min_score must be at least 1, not %r' % (terminal_min_score,))
     if consensus_insertions and consensus is None:
         raise ValueError('consensus_insertions needs consensus: there is no library to insert into')
     if (families is not None or consensus is not None or family_alignments is not None or copy_divergence is not None or landscape is not None) and \
@@ -611,6 +640,14 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
                     with open(path, 'w') as f:
                         for line in make(members):
                             f.write(line + '\n')
+    if terminal_repeats is not None:
+        none = np.zeros(0, dtype=engine._ffi.INTERVAL)
+        tl = terminal_block(A, reg_main[0] if reg_main else none, str(prefix), terminal_window, terminal_min_score, True)
+        if splitSelf:   # the intra lines follow, with their restarted IDs, as in the GFF3
+            tl += terminal_block(A, reg_intra[0] if reg_intra else none, str(prefix), terminal_window, terminal_min_score, False)
+        with open(terminal_repeats, 'w') as f:
+            for line in tl:
+                f.write(line + '\n')
     return lines
 
 
