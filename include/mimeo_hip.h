@@ -815,6 +815,71 @@ int mimeo_terminal_repeats(const mimeo_genome *G, const mimeo_interval *iv, uint
                            uint64_t **path_first /* 2 n + 1 */, mimeo_path_block **blocks, uint64_t *nblocks);
 
 /*
+ * Flank repeats (kernel K18): the target-site duplication of an element.  An insertion duplicates 2 - 20 bases of the host;
+ * the two copies lie immediately outside the element's two ends, in direct orientation.  Finding them is the evidence that
+ * a pair of terminal repeats (mimeo_terminal_repeats) is an insertion, and it fixes the element's first and last base, which a
+ * local alignment with a score cut-off cannot.
+ *
+ * Item [start, end) on scaffold `chrom` of G, of length L; fwd is the scaffold's forward strand.
+ *   candidates   every dl, dr in [-slack, slack] and every k in [min_len, max_len]
+ *   copies       p = start + dl - k is the start of the left copy, r = end + dr the start of the right copy
+ *   admissible   p >= 0, r + k <= L and start + dl <= end + dr;
+ *                m <= max_mismatch, with m the number of columns c in [0, k) where fwd[p + c] and fwd[r + c] are not two
+ *                equal ACGT bases;
+ *                columns 0 and k - 1 match;
+ *                v = k - 3 m >= min_len
+ *   choice       the admissible candidate with the largest v; of equal ones the smallest |dl| + |dr|, then the smallest m,
+ *                then the smallest dl, then the smallest dr
+ * The record: left_start = p, right_start = r, len = k, mismatches = m, dl, dr; the element is [start + dl, end + dr).  No
+ * admissible candidate: the record is all zero (len == 0 tells).
+ *
+ * `out` is the caller's, n records.  Everything is checked before the device sees it, and reported as MIMEO_ERR_ARG with a
+ * message that starts with "mimeo_flank_repeats:" and names the item: a chrom outside the genome, an item that is not
+ * start <= end <= L, a parameter out of range, a reserved field that is not 0.  n == 0 returns MIMEO_OK at once.  The
+ * results are exact and do not depend on how the items are batched.
+ *
+ * Chance (derived, not measured): with max_mismatch 0 a candidate (dl, dr) holds a duplication of at least min_len bases
+ * with probability 4^-min_len, and the maximal runs of a diagonal add the factor 1 + 1/4 + ... = 4/3, so a random site has
+ * at most (2 slack + 1)^2 * 4^-min_len * 4/3 admissible candidates: 0.13 at the defaults (in a restatement 0.073 of 2000 random
+ * sites had one: candidates that share a diagonal come together).  A 4-base duplication is weak evidence, a 6-base one strong.
+ *
+ * mimeo_open_frames (kernel K19): the longest stop-free stretch of each of the six reading frames of an item.
+ * Item [start, end) has m = end - start bases on a scaffold of length L.
+ *   strands   sigma = 0: s[i] = fwd[start + i]; sigma = 1: s[i] = rc[L - end + i] — a window of the stored reverse complement;
+ *             nothing is flipped, as in mimeo_terminal_repeats
+ *   codons    in frame phi in {0, 1, 2} codon t is s[phi + 3t .. phi + 3t + 2], 0 <= t < T = max(0, (m - phi) / 3), integer
+ *             division.  A codon is closed when it is TAA, TAG or TGA, or when any of its bases is not ACGT (an N run is no
+ *             open frame); otherwise it is open
+ *   record    out[6k + 3 sigma + phi]: the longest maximal run [t0, t1) of open codons, the earliest t0 among runs of equal
+ *             length.  codons = t1 - t0; [start, end) on the plus strand is [start + phi + 3 t0, start + phi + 3 t1) for
+ *             sigma = 0 and [end - phi - 3 t1, end - phi - 3 t0) for sigma = 1; met is the index within the run of its first
+ *             ATG codon, and equals codons when the run has none.  A frame with no open codon has an all-zero record.
+ * The checks and the message convention are those of mimeo_flank_repeats, with the prefix "mimeo_open_frames:"; flags that are
+ * not 0 are MIMEO_ERR_ARG.  The results are exact and do not depend on how an item is cut into chunks.
+ *
+ * Three new symbols beside the old ones: MIMEO_ABI_VERSION stays 3; a host that needs them checks for the symbols.
+ */
+typedef struct mimeo_flank_params {
+    int32_t min_len;       /* [4]  2 .. 32: shortest duplication reported (after the mismatch charge, above) */
+    int32_t max_len;       /* [20] min_len .. 32                                                            */
+    int32_t slack;         /* [2]  0 .. 8: how far either element boundary may move                          */
+    int32_t max_mismatch;  /* [0]  0 .. 2                                                                   */
+    int32_t reserved[4];   /* must be 0 */
+} mimeo_flank_params;
+typedef struct mimeo_flank_repeat {   /* 16 bytes */
+    uint32_t left_start, right_start; /* the two copies [left_start, left_start+len), [right_start, right_start+len), plus strand */
+    uint16_t len, mismatches;
+    int8_t   dl, dr;                  /* the element is [start + dl, end + dr) */
+    uint16_t reserved;
+} mimeo_flank_repeat;
+int mimeo_flank_params_default(mimeo_flank_params *p);
+int mimeo_flank_repeats(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n,
+                        const mimeo_flank_params *p, mimeo_flank_repeat *out /* caller's, n */);
+typedef struct mimeo_open_frame { uint32_t start, end, codons, met; } mimeo_open_frame;   /* 16 bytes */
+int mimeo_open_frames(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n, uint32_t flags /* must be 0 */,
+                      mimeo_open_frame *out /* caller's, 6 n: out[6k + 3 sigma + phi] */);
+
+/*
  * Pairs of the last mimeo_align_pairs / mimeo_align_units call that hit a documented limit and were left
  * out: *n of them; the first min(*n, cap) are written to pair_index[] (index into the call's pair list)
  * and code[] (MIMEO_ERR_LIMIT).  Either array may be NULL.  A left-out pair is a scaffold pair: EVERY entry of the

@@ -167,6 +167,45 @@ def check_terminal(parser, args):
     return args
 
 
+def add_elements(parser):
+    """--elements and its parameters of `mimeo self` (the features of `mimeo x` lie in another genome)"""
+    parser.add_argument('--elements', type=str, default=None, metavar='FILE',
+                        help='Also write to FILE, tab-separated, one structural line per feature of the GFF3: the terminal repeats of '
+                             '--terminalRepeats (kind LTR or TIR; --terminalWindow and --terminalMinScore apply, --terminalRepeats need not be '
+                             'given), the target-site duplication (TSD) immediately outside them - the short direct repeat of host sequence '
+                             'that the insertion made, which fixes the element\'s first and last base (el_start, el_end) - the longest open '
+                             'reading frame inside the element over its six frames, and a class: LTR_retrotransposon, LTR_nonautonomous, '
+                             'LTR_candidate (no TSD), DNA_transposon, MITE (a non-coding TIR element of at most 800 bases), '
+                             'DNA_nonautonomous, TIR_candidate (no TSD), coding_repeat. TSDs and frames are found on the GPU. With --tsdMismatch '
+                             '0 a random site has at most (2*tsdSlack+1)^2 * 4^-tsdMin * 4/3 chance candidates, 0.13 at the defaults '
+                             '(derived; 0.073 of 2000 random sites had one in a restatement): a 4-base TSD is weak evidence, a 6-base one strong - '
+                             'the file reports tsd_len. Off by default.')
+    parser.add_argument('--tsdMin', type=int, default=4, metavar='N', help='Shortest TSD that --elements reports, after 3 bases are charged per mismatch (2..32). Default: 4')
+    parser.add_argument('--tsdMax', type=int, default=20, metavar='N', help='Longest TSD that --elements looks for (tsdMin..32). Default: 20')
+    parser.add_argument('--tsdSlack', type=int, default=2, metavar='N',
+                        help='Bases by which either end of the terminal-repeat pair may move to meet the TSD (0..8). Default: 2')
+    parser.add_argument('--tsdMismatch', type=int, default=0, metavar='N', help='Mismatches allowed inside a TSD, never in its end columns (0..2). Default: 0')
+    parser.add_argument('--elementMinOrf', type=int, default=300, metavar='CODONS',
+                        help='Codons from which the longest open frame makes an element coding for the class of --elements. A random open run '
+                             'reaches 300 codons with probability (61/64)^300, about 6e-7 per start; at 100 codons it is 0.8 per cent. Default: 300')
+
+
+def check_elements(parser, args):
+    """the ranges of --tsdMin, --tsdMax, --tsdSlack, --tsdMismatch and --elementMinOrf (parser.error exits with status 2, before
+    the engine starts)"""
+    if not 2 <= args.tsdMin <= 32:
+        parser.error('--tsdMin must be in 2..32')
+    if not args.tsdMin <= args.tsdMax <= 32:
+        parser.error('--tsdMax must be in tsdMin..32')
+    if not 0 <= args.tsdSlack <= 8:
+        parser.error('--tsdSlack must be in 0..8')
+    if not 0 <= args.tsdMismatch <= 2:
+        parser.error('--tsdMismatch must be in 0..2')
+    if args.elementMinOrf < 1:
+        parser.error('--elementMinOrf must be at least 1')
+    return args
+
+
 def check_consensus(parser, args):
     """--consensusInsertions of `mimeo self` (parser.error exits with status 2, before the engine starts)"""
     if args.consensusInsertions and args.consensus is None:

@@ -21,7 +21,7 @@ SYMBOLS = [
     'mimeo_align_units', 'mimeo_get_failed_pairs', 'mimeo_chain_hsps', 'mimeo_align_units_paths', 'mimeo_path_stats',
     'mimeo_path_window_stats', 'mimeo_path_text', 'mimeo_link_regions', 'mimeo_path_pileup',
     'mimeo_path_insertions', 'mimeo_path_stack', 'mimeo_path_call_stats', 'mimeo_terminal_params_default',
-    'mimeo_terminal_repeats',
+    'mimeo_terminal_repeats', 'mimeo_flank_params_default', 'mimeo_flank_repeats', 'mimeo_open_frames',
 ]
 
 
@@ -51,7 +51,12 @@ class TerminalParams(C.Structure):   # mimeo_terminal_params, 32 bytes
     NAMES = ('window', 'match', 'mismatch', 'gap_open', 'gap_extend', 'min_score')
 
 
-ANCHOR_BOX, ANCHOR_PATH = 0, 1   # Params.anchor_rule (MIMEO_ANCHOR_*)
+class FlankParams(C.Structure):   # mimeo_flank_params, 32 bytes
+    _fields_ = [(n, C.c_int32) for n in ('min_len', 'max_len', 'slack', 'max_mismatch')] + [('reserved', C.c_int32 * 4)]
+    NAMES = ('min_len', 'max_len', 'slack', 'max_mismatch')
+
+
+ANCHOR_BOX, ANCHOR_PATH = 0, 1  # Params.anchor_rule (MIMEO_ANCHOR_*)
 ANCHOR_RULES = {'box': ANCHOR_BOX, 'path': ANCHOR_PATH}
 
 
@@ -87,6 +92,9 @@ INSERT_MAX_COLS = 1024   # insertion columns of one site, at most (include/mimeo
 STACK_ROW = np.dtype([(n, '<u4') for n in ('q_lo', 'q_hi', 'bases', 'hidden')])   # mimeo_stack_row, 16 bytes
 CALL_STATS = np.dtype([(n, '<u4') for n in ('matches', 'transitions', 'transversions', 'ambiguous', 'ins_bases', 'del_bases', 'q_lo',
                                              'q_hi')])   # mimeo_call_stats, 32 bytes
+FLANK_REPEAT = np.dtype([('left_start', '<u4'), ('right_start', '<u4'), ('len', '<u2'), ('mismatches', '<u2'), ('dl', 'i1'), ('dr', 'i1'),
+                         ('reserved', '<u2')])   # mimeo_flank_repeat, 16 bytes
+OPEN_FRAME = np.dtype([(n, '<u4') for n in ('start', 'end', 'codons', 'met')])   # mimeo_open_frame, 16 bytes
 DEPTH_RUN = np.dtype([('chrom', '<u4'), ('start', '<u4'), ('end', '<u4'), ('depth', '<u4')])
 
 _lib = None
@@ -151,6 +159,11 @@ def load():
     if hasattr(lib, 'mimeo_terminal_repeats'):
         lib.mimeo_terminal_params_default.argtypes = [C.POINTER(TerminalParams)]
         lib.mimeo_terminal_repeats.argtypes = [vp, vp, u64, C.POINTER(TerminalParams), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    if hasattr(lib, 'mimeo_flank_repeats'):
+        lib.mimeo_flank_params_default.argtypes = [C.POINTER(FlankParams)]
+        lib.mimeo_flank_repeats.argtypes = [vp, vp, u64, C.POINTER(FlankParams), vp]
+    if hasattr(lib, 'mimeo_open_frames'):
+        lib.mimeo_open_frames.argtypes = [vp, vp, u64, u32, vp]
     if hasattr(lib, 'mimeo_chain_hsps'):
         lib.mimeo_chain_hsps.argtypes = [vp, u64, vp]
     if hasattr(lib, 'mimeo_coverage_collapse'):

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "terminal_host.h"
+#include "flank_host.h"
 
 namespace mimeo {
 
@@ -493,6 +494,32 @@ int mimeo_terminal_repeats(const mimeo_genome *G, const mimeo_interval *iv, uint
         return MIMEO_ERR_ARG;
     }
     return terminal_repeats_device(G, iv, n, p, out, path_first, blocks, nblocks);
+}
+
+int mimeo_flank_params_default(mimeo_flank_params *p) {
+    if (!p) { set_error("mimeo_flank_params_default: null argument"); return MIMEO_ERR_ARG; }
+    flank_host::defaults(p);
+    return MIMEO_OK;
+}
+
+int mimeo_flank_repeats(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n, const mimeo_flank_params *p, mimeo_flank_repeat *out) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!G || !p || (n && (!iv || !out))) {
+        set_error("mimeo_flank_repeats: null argument");
+        return MIMEO_ERR_ARG;
+    }
+    return flank_repeats_device(G, iv, n, p, out);
+}
+
+int mimeo_open_frames(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n, uint32_t flags, mimeo_open_frame *out) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!G || (n && (!iv || !out))) {
+        set_error("mimeo_open_frames: null argument");
+        return MIMEO_ERR_ARG;
+    }
+    return open_frames_device(G, iv, n, flags, out);
 }
 
 int mimeo_get_failed_pairs(uint64_t *pair_index, int32_t *code, uint64_t cap, uint64_t *n) {

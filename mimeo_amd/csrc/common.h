@@ -398,4 +398,8 @@ int path_call_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const m
 // `out`, two malloc'ed arrays out.
 int terminal_repeats_device(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n, const mimeo_terminal_params *p, mimeo_alignment *out,
                             uint64_t **path_first, mimeo_path_block **blocks, uint64_t *nblocks);
+// K18: the target-site duplication at the two ends of every item (k18_flank.hip); host in, records into the caller's `out`.
+int flank_repeats_device(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n, const mimeo_flank_params *p, mimeo_flank_repeat *out);
+// K19: the longest open run of the six reading frames of every item (k19_frames.hip); host in, 6 n records into the caller's `out`.
+int open_frames_device(const mimeo_genome *G, const mimeo_interval *iv, uint64_t n, uint32_t flags, mimeo_open_frame *out);
 }  // namespace mimeo

@@ -468,6 +468,54 @@ def terminal_repeats(A, intervals, **params):
     return recs, _ffi.take(pf, C.c_uint64(2 * iv.size + 1), np.dtype('<u8')), _ffi.take(pb, nb, _ffi.PATH_BLOCK)
 
 
+def _intervals(intervals):
+    iv = np.asarray(intervals)
+    if iv.dtype != _ffi.INTERVAL:
+        a = np.asarray(iv, dtype=np.uint32).reshape(-1, 3)
+        iv = np.zeros(a.shape[0], dtype=_ffi.INTERVAL)
+        iv['chrom'], iv['start'], iv['end'] = a[:, 0], a[:, 1], a[:, 2]
+    return np.ascontiguousarray(iv)
+
+
+def flank_repeats(A, intervals, **params):
+    """Flank repeats (mimeo_flank_repeats, kernel K18): for every (scaffold id, start, end) of genome A the target-site duplication
+    of the element — the direct repeat of min_len .. max_len bases immediately outside its two ends, either end free to move by
+    up to `slack` bases.  Returns one record of _ffi.FLANK_REPEAT per interval: the two copies [left_start, left_start + len) and
+    [right_start, right_start + len), mismatches, and dl, dr: the element is [start + dl, end + dr); all zero (len 0) where there
+    is none.  params: min_len (4; 2 .. 32), max_len (20; min_len .. 32), slack (2; 0 .. 8), max_mismatch (0; 0 .. 2) —
+    include/mimeo_hip.h has the rules, ties included.  A bad parameter or item is a RuntimeError naming it, raised before anything
+    runs on the device."""
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_flank_repeats'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_flank_repeats: rebuild the library')
+    P = _ffi.FlankParams()
+    _ffi.check(lib.mimeo_flank_params_default(C.byref(P)))
+    for k, v in params.items():
+        if k not in _ffi.FlankParams.NAMES:
+            raise TypeError('unknown flank-repeat parameter %r' % k)
+        setattr(P, k, int(v))
+    iv = _intervals(intervals)
+    out = np.zeros(iv.size, dtype=_ffi.FLANK_REPEAT)
+    _ffi.check(lib.mimeo_flank_repeats(A._h, iv.ctypes.data if iv.size else None, iv.size, C.byref(P), out.ctypes.data if iv.size else None))
+    return out
+
+
+def open_frames(A, intervals):
+    """Open frames (mimeo_open_frames, kernel K19): for every (scaffold id, start, end) of genome A and each of its six reading
+    frames the longest run of codons without a stop and without a non-ACGT base.  Returns an array of shape (n, 6) of
+    _ffi.OPEN_FRAME, column 3 * strand + frame (strand 1: the reverse complement; frame: the offset of the first codon from the
+    interval's 5' end on that strand): start, end on the plus strand, codons, and met — the index within the run of its first ATG,
+    codons where it has none; all zero for a frame without an open codon.  include/mimeo_hip.h has the rules.  A bad item is a
+    RuntimeError naming it, raised before anything runs on the device."""
+    lib = _ffi.load()
+    if not hasattr(lib, 'mimeo_open_frames'):
+        raise RuntimeError('libmimeo_hip.so has no mimeo_open_frames: rebuild the library')
+    iv = _intervals(intervals)
+    out = np.zeros((iv.size, 6), dtype=_ffi.OPEN_FRAME)
+    _ffi.check(lib.mimeo_open_frames(A._h, iv.ctypes.data if iv.size else None, iv.size, 0, out.ctypes.data if iv.size else None))
+    return out
+
+
 def failed_pairs():
     """Pairs of the last align_pairs / align_units call that hit a documented limit and were left out (the reference's script
     loses only the failing lastz run's rows: utils.py:125-128): [(index into the call's pair list, error code)]."""

@@ -465,6 +465,55 @@ def terminal_repeat_lines(regions, names_sorted, prefix, window, records, stats,
     return lines
 
 
+ELEMENTS_HEADER = '\t'.join(('#feature', 'seqid', 'start', 'end', 'kind', 'el_start', 'el_end', 'left_len', 'right_len', 'tr_score', 'tr_identity', 'tr_kd',
+                             'tsd_len', 'tsd', 'tsd_mismatches', 'tsd_shift', 'ends', 'orf_strand', 'orf_frame', 'orf_start', 'orf_end', 'orf_codons',
+                             'orf_met_codons', 'class'))
+MITE_MAX_LEN = 800   # a non-coding TIR element with a duplication is a MITE up to this length, DNA_nonautonomous beyond it
+
+
+def element_class(kind, has_tsd, coding, length):
+    """the class column of --elements: the first rule that applies"""
+    if kind == 'LTR':
+        return ('LTR_retrotransposon' if coding else 'LTR_nonautonomous') if has_tsd else 'LTR_candidate'
+    if kind == 'TIR':
+        if not has_tsd:
+            return 'TIR_candidate'
+        return 'DNA_transposon' if coding else 'MITE' if length <= MITE_MAX_LEN else 'DNA_nonautonomous'
+    return 'coding_repeat' if coding else '.'
+
+
+def element_lines(regions, names_sorted, prefix, rows, min_orf=300, header=True):
+    """--elements: ELEMENTS_HEADER (header=True), then one tab-separated line per region, in the order of the GFF3 rows.  ID,
+    seqid, start and end are those of the region's GFF3 row, as in terminal_repeat_lines.  rows: per region a dict (what
+    workflow.elements_block puts together from kernels K17, K9, K18 and K19) with
+      kind      'LTR', 'TIR' or None: the orientation of the terminal repeats that was chosen; with a kind also left_len,
+                right_len (bases of the two repeats), score and stats (the record's row of engine.path_stats: tr_identity =
+                matches / columns, tr_kd Kimura's distance as in terminal_repeat_lines)
+      el        (el_start, el_end): the element, the feature itself where there is no kind
+      tsd       None or (len, letters of the left copy, mismatches, dl, dr); tsd_shift prints dl,dr
+      ends      the element's first two and last two bases as TG..CA, None for an empty element
+      orf       None or (strand 0 / 1, frame 0 .. 2, start, end, codons, met): the best of the six frames — most codons, then
+                the plus strand, then the lower frame; orf_frame prints 1 .. 3 and orf_met_codons codons - met, the codons
+                from the run's first ATG on (0: none)
+    class: element_class, where coding means orf_codons >= min_orf.  A value that is undefined prints as '.'."""
+    lines = [ELEMENTS_HEADER] if header else []
+    for i, (r, w) in enumerate(zip(regions, rows), 1):
+        kind, tsd, orf, (el0, el1) = w['kind'], w['tsd'], w['orf'], w['el']
+        tr = ['.'] * 5
+        if kind is not None:
+            s = w['stats']
+            columns = sum(int(s[f]) for f in ('matches', 'transitions', 'transversions', 'ambiguous'))
+            kd = divergence_values(s)[3]
+            tr = [str(int(w['left_len'])), str(int(w['right_len'])), str(int(w['score'])), '%.4f' % (int(s['matches']) / columns) if columns else '.',
+                  '%.4f' % kd if kd is not None else '.']
+        td = ['.'] * 4 if tsd is None else [str(int(tsd[0])), tsd[1], str(int(tsd[2])), '%d,%d' % (tsd[3], tsd[4])]
+        of = ['.'] * 6 if orf is None else ['+-'[orf[0]], str(orf[1] + 1), str(orf[2]), str(orf[3]), str(orf[4]), str(orf[4] - orf[5])]
+        cls = element_class(kind, tsd is not None, orf is not None and orf[4] >= int(min_orf), el1 - el0)
+        lines.append('\t'.join(['%s_%05d' % (prefix, i), names_sorted[int(r['chrom'])], str(int(r['start'])), str(int(r['end'])), kind or '.', str(el0), str(el1)] +
+                               tr + td + [w['ends'] or '.'] + of + [cls]))
+    return lines
+
+
 FAMILY_HEADER = '\t'.join(('#ID', 'seqid', 'start', 'end', 'family', 'members', 'family_bases', 'links'))
 
 

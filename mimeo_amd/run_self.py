@@ -18,12 +18,13 @@ def mainArgs(argv=None):
     _cli.add_family_alignments(parser)
     _cli.add_copy_divergence(parser)
     _cli.add_terminal_repeats(parser)
+    _cli.add_elements(parser)
     parser.add_argument('--minCov', type=int, default=3, help='Minimum depth of aligned segments to report repeat feature.')
     parser.add_argument('--intraCov', type=int, default=5,
                         help='Minimum depth of aligned segments from same scaffold to report feature. Used if "--strictSelf" mode is selected.')
     parser.add_argument('--strictSelf', action='store_true',
                         help='If set process same-scaffold alignments separately with option to use higher "--intraCov" threshold.')
-    return _cli.check_terminal(parser, _cli.check_consensus(parser, _cli.check_families(parser, _cli.check_common(parser, parser.parse_args(argv)))))
+    return _cli.check_elements(parser, _cli.check_terminal(parser, _cli.check_consensus(parser, _cli.check_families(parser, _cli.check_common(parser, parser.parse_args(argv))))))
 
 
 def main(argv=None):
@@ -44,7 +45,9 @@ def main(argv=None):
                           region_stats=args.regionStats, maf=args.maf, cs=args.cs, families=args.families, family_cover=args.familyCover,
                           consensus=args.consensus, consensus_insertions=args.consensusInsertions, family_alignments=args.familyAlignments,
                           copy_divergence=args.copyDivergence, landscape=args.landscape,
-                          terminal_repeats=args.terminalRepeats, terminal_window=args.terminalWindow, terminal_min_score=args.terminalMinScore)
+                          terminal_repeats=args.terminalRepeats, terminal_window=args.terminalWindow, terminal_min_score=args.terminalMinScore,
+                          elements=args.elements, tsd_min=args.tsdMin, tsd_max=args.tsdMax, tsd_slack=args.tsdSlack, tsd_mismatch=args.tsdMismatch,
+                          element_min_orf=args.elementMinOrf)
     if args.verbose:
         logging.info('engine stats: %s', engine.stats())
     A.close()

@@ -268,10 +268,10 @@ def region_stat_block(A, B, kept_paths, select, regions, prefix, header):
     return formats.region_stat_lines(regions, names_sorted, prefix, stats, per_region, header=header)
 
 
-def terminal_block(A, regions, prefix, window, min_score, header):
-    """--terminalRepeats for one block of GFF3 rows: the regions as intervals of their scaffolds, one engine.terminal_repeats
-    call (kernel K17: each region's head against its tail, direct and inverted), one engine.path_stats call (K9) over the
-    returned records, the lines of formats.terminal_repeat_lines.  Needs no alignment of the job: only the regions."""
+def terminal_calls(A, regions, window, min_score):
+    """What --terminalRepeats and --elements share for one block of GFF3 rows: the regions as intervals of their scaffolds, one
+    engine.terminal_repeats call (kernel K17: each region's head against its tail, direct and inverted) and one
+    engine.path_stats call (K9) over the returned records.  Returns (names_sorted, intervals, records, stats)."""
     names_sorted = sorted(A.names, key=lambda s: s.encode())
     tid = {n: i for i, n in enumerate(A.names)}
     iv = np.zeros(len(regions), dtype=engine._ffi.INTERVAL)
@@ -279,8 +279,91 @@ def terminal_block(A, regions, prefix, window, min_score, header):
         iv['chrom'] = [tid[names_sorted[int(c)]] for c in regions['chrom']]
         iv['start'], iv['end'] = regions['start'], regions['end']
     recs, first, blk = engine.terminal_repeats(A, iv, window=int(window), min_score=int(min_score))
-    stats = engine.path_stats(A, None, recs, first, blk)
+    return names_sorted, iv, recs, engine.path_stats(A, None, recs, first, blk)
+
+
+def terminal_block(A, regions, prefix, window, min_score, header, calls=None):
+    """--terminalRepeats for one block of GFF3 rows: terminal_calls (or what it returned, `calls`, where --elements made the
+    calls already) and the lines of formats.terminal_repeat_lines.  Needs no alignment of the job: only the regions."""
+    names_sorted, _, recs, stats = calls if calls is not None else terminal_calls(A, regions, window, min_score)
     return formats.terminal_repeat_lines(regions, names_sorted, prefix, window, recs, stats, header=header)
+
+
+def genome_letters(A, spans):
+    """The letters (A C G T, N for everything else) of the plus-strand stretches (scaffold id, start, end), end > start, of the
+    resident genome: one engine.path_text call (K11) over one-block paths of each stretch against itself."""
+    n = len(spans)
+    if not n:
+        return []
+    s = np.asarray(spans, dtype=np.int64).reshape(-1, 3)
+    recs = np.zeros(n, dtype=engine._ffi.ALIGNMENT)
+    recs['tid'] = recs['qid'] = s[:, 0]
+    recs['tstart'] = recs['qstart'] = s[:, 1]
+    recs['tend'] = recs['qend'] = s[:, 2]
+    recs['id_n'] = recs['id_d'] = s[:, 2] - s[:, 1]
+    blk = np.zeros(n, dtype=engine._ffi.PATH_BLOCK)
+    blk['t'] = blk['q'] = s[:, 1]
+    blk['len'] = s[:, 2] - s[:, 1]
+    rf, trow, _ = engine.path_text(A, None, recs, np.arange(n + 1, dtype=np.uint64), blk)
+    return [bytes(trow[int(rf[i]):int(rf[i + 1])]).decode() for i in range(n)]
+
+
+def elements_block(A, regions, prefix, window, min_score, tsd, min_orf, header, calls=None):
+    """--elements for one block of GFF3 rows (the lines of formats.element_lines): (1) terminal_calls — K17 over the regions, K9
+    over its records; (2) for every orientation found the element is [tstart, qend), and one engine.flank_repeats call (K18,
+    parameters `tsd`: min_len, max_len, slack, max_mismatch) covers all of them; (3) per feature the orientation with a
+    target-site duplication is chosen — both or neither: the higher K17 score, then LTR; (4) the element is
+    [tstart + dl, qend + dr), the feature itself where no orientation was found; (5) one engine.open_frames call (K19) covers
+    the n elements; (6) the letters of the duplications and of the elements' ends come from the resident genome
+    (genome_letters).  Needs no alignment of the job: only the regions."""
+    names_sorted, iv, recs, stats = calls if calls is not None else terminal_calls(A, regions, window, min_score)
+    n = len(regions)
+    found = [(k, o) for k in range(n) for o in (0, 1) if int(recs[2 * k + o]['id_d']) > 0]
+    span = np.zeros(len(found), dtype=engine._ffi.INTERVAL)
+    for j, (k, o) in enumerate(found):
+        span[j] = (iv[k]['chrom'], recs[2 * k + o]['tstart'], recs[2 * k + o]['qend'])
+    fl = engine.flank_repeats(A, span, **tsd)
+    cands = [[] for _ in range(n)]
+    for j, (k, o) in enumerate(found):
+        cands[k].append((o, j))
+    rows, el = [], np.zeros(n, dtype=engine._ffi.INTERVAL)
+    el[:] = iv
+    for k in range(n):
+        with_tsd = [c for c in cands[k] if int(fl[c[1]]['len'])]
+        pool = with_tsd if len(with_tsd) == 1 else cands[k]
+        row = dict(kind=None, tsd=None)
+        if pool:
+            o, j = min(pool, key=lambda c: (-int(recs[2 * k + c[0]]['score']), c[0]))
+            a, f = recs[2 * k + o], fl[j]
+            el[k]['start'], el[k]['end'] = int(span[j]['start']) + int(f['dl']), int(span[j]['end']) + int(f['dr'])
+            row.update(kind=formats.TERMINAL_KINDS[o], left_len=int(a['tend']) - int(a['tstart']), right_len=int(a['qend']) - int(a['qstart']),
+                       score=int(a['score']), stats=stats[2 * k + o])
+            if int(f['len']):
+                row['tsd'] = [int(f['len']), (int(iv[k]['chrom']), int(f['left_start']), int(f['left_start']) + int(f['len'])), int(f['mismatches']), int(f['dl']),
+                              int(f['dr'])]
+        row['el'] = (int(el[k]['start']), int(el[k]['end']))
+        rows.append(row)
+    fr = engine.open_frames(A, el)
+    want = []   # (row, what, stretch)
+    for k, row in enumerate(rows):
+        c, (a, b) = int(iv[k]['chrom']), row['el']
+        if row['tsd'] is not None:
+            want.append((k, 'tsd', row['tsd'][1]))
+        if b > a:
+            want += [(k, 'head', (c, a, min(a + 2, b))), (k, 'tail', (c, max(b - 2, a), b))]
+        f = min(range(6), key=lambda j: (-int(fr[k, j]['codons']), j))
+        row['orf'] = (f // 3, f % 3, int(fr[k, f]['start']), int(fr[k, f]['end']), int(fr[k, f]['codons']), int(fr[k, f]['met'])) if int(fr[k, f]['codons']) else None
+        row['ends'] = None
+    ends = {}
+    for (k, what, _), text in zip(want, genome_letters(A, [w[2] for w in want])):
+        if what == 'tsd':
+            rows[k]['tsd'][1] = text
+        else:
+            ends[(k, what)] = text
+    for k, row in enumerate(rows):
+        if (k, 'head') in ends:
+            row['ends'] = ends[(k, 'head')] + '..' + ends[(k, 'tail')]
+    return formats.element_lines(regions, names_sorted, prefix, rows, min_orf, header=header)
 
 
 def family_block(A, kept_paths, select, regions, prefix, cover, suffix, header):
@@ -449,7 +532,8 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
                  B=None, anchor_rule='box', bound_extensions=False, paf=None, divergence=False, region_stats=None, maf=None, cs=False,
                  text_budget=TEXT_BUDGET, families=None, family_cover=80, consensus=None, consensus_budget=CONSENSUS_BUDGET,
                  consensus_insertions=False, family_alignments=None, stack_budget=STACK_BUDGET, copy_divergence=None, landscape=None,
-                 terminal_repeats=None, terminal_window=1024, terminal_min_score=40):
+                 terminal_repeats=None, terminal_window=1024, terminal_min_score=40, elements=None, tsd_min=4, tsd_max=20, tsd_slack=2, tsd_mismatch=0,
+                 element_min_orf=300):
     """`mimeo self` (and, with B and source='mimeo', `mimeo x`).  paf: also write the rows of the TAB as PAF with their
     CIGARs to this file (--paf; nothing when the TAB is recycled); divergence: with paf, every PAF row also carries its
     divergence tags (--divergence; formats.divergence_tags).  anchor_rule: the gapped stage's skip rule, 'box' or
@@ -495,7 +579,14 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
     of features"): the first terminal_window bases of the region against its last, direct (kind LTR) and inverted (kind TIR), a
     full affine-gap local alignment each, reported from a score of terminal_min_score on.  It needs the regions alone — none of
     paf, families or consensus, no paths, and it works with a recycled TAB; on rank 0, no collective; with splitSelf the intra
-    block's lines follow; every other output is unchanged."""
+    block's lines follow; every other output is unchanged.  elements (`mimeo self` only: ValueError with B): also write, to this
+    file, one structural line per GFF3 row (--elements; elements_block, formats.element_lines): the terminal repeats of K17
+    (terminal_window and terminal_min_score apply; terminal_repeats need not be given, and where it is the block's K17 and K9
+    calls are shared), the target-site duplication just outside them (kernel K18, include/mimeo_hip.h "Flank repeats": tsd_min ..
+    tsd_max bases, either end free to move by tsd_slack bases, at most tsd_mismatch mismatches), which fixes the element's first
+    and last base, the longest open reading frame inside the element (kernel K19) and a class, where an element is coding from
+    element_min_orf codons on.  Like terminal_repeats it needs the regions alone; on rank 0, no collective; with splitSelf the
+    intra block's lines follow; every other output is unchanged."""
     dist = dist or Dist()
     cs = cs and paf is not None
     if families is not None and B is not None:
@@ -515,6 +606,23 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
             raise ValueError('terminal_window must be in 1..4096, not %r' % (terminal_window,))
         if int(terminal_min_score) < 1:
             raise ValueError('terminal_min_score must be at least 1, not %r' % (terminal_min_score,))
+    if elements is not None:
+        if B is not None:
+            raise ValueError('elements needs a self job: the regions must lie in the genome that was aligned to itself')
+        if not 1 <= int(terminal_window) <= 4096:
+            raise ValueError('terminal_window must be in 1..4096, not %r' % (terminal_window,))
+        if int(terminal_min_score) < 1:
+            raise ValueError('terminal_min_score must be at least 1, not %r' % (terminal_min_score,))
+        if not 2 <= int(tsd_min) <= 32:
+            raise ValueError('tsd_min must be in 2..32, not %r' % (tsd_min,))
+        if not int(tsd_min) <= int(tsd_max) <= 32:
+            raise ValueError('tsd_max must be in tsd_min..32, not %r' % (tsd_max,))
+        if not 0 <= int(tsd_slack) <= 8:
+            raise ValueError('tsd_slack must be in 0..8, not %r' % (tsd_slack,))
+        if not 0 <= int(tsd_mismatch) <= 2:
+            raise ValueError('tsd_mismatch must be in 0..2, not %r' % (tsd_mismatch,))
+        if int(element_min_orf) < 1:
+            raise ValueError('element_min_orf must be at least 1, not %r' % (element_min_orf,))
     if consensus_insertions and consensus is None:
         raise ValueError('consensus_insertions needs consensus: there is no library to insert into')
     if (families is not None or consensus is not None or family_alignments is not None or copy_divergence is not None or landscape is not None) and \
@@ -640,14 +748,23 @@ def self_repeats(A, pairs, outtab, outgff, minIdt=60, minLen=100, hspthresh=3000
                     with open(path, 'w') as f:
                         for line in make(members):
                             f.write(line + '\n')
-    if terminal_repeats is not None:
+    if terminal_repeats is not None or elements is not None:
         none = np.zeros(0, dtype=engine._ffi.INTERVAL)
-        tl = terminal_block(A, reg_main[0] if reg_main else none, str(prefix), terminal_window, terminal_min_score, True)
-        if splitSelf:   # the intra lines follow, with their restarted IDs, as in the GFF3
-            tl += terminal_block(A, reg_intra[0] if reg_intra else none, str(prefix), terminal_window, terminal_min_score, False)
-        with open(terminal_repeats, 'w') as f:
-            for line in tl:
-                f.write(line + '\n')
+        tsd = dict(min_len=int(tsd_min), max_len=int(tsd_max), slack=int(tsd_slack), max_mismatch=int(tsd_mismatch))
+        tl, el = [], []
+        # the intra lines follow, with their restarted IDs, as in the GFF3
+        for regs, header in ((reg_main, True), (reg_intra, False)) if splitSelf else ((reg_main, True),):
+            regs = regs[0] if regs else none
+            calls = terminal_calls(A, regs, terminal_window, terminal_min_score) if elements is not None else None   # one K17 and one K9 call for both files
+            if terminal_repeats is not None:
+                tl += terminal_block(A, regs, str(prefix), terminal_window, terminal_min_score, header, calls=calls)
+            if elements is not None:
+                el += elements_block(A, regs, str(prefix), terminal_window, terminal_min_score, tsd, int(element_min_orf), header, calls=calls)
+        for path, out in ((terminal_repeats, tl), (elements, el)):
+            if path is not None:
+                with open(path, 'w') as f:
+                    for line in out:
+                        f.write(line + '\n')
     return lines
 
 

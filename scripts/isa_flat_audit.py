@@ -20,7 +20,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'mimeo_amd', 'csrc')
-FILES = ['k34_fused.hip', 'k4_extend.hip', 'k5_chain.hip', 'k5_wave.hip', 'k6_gapped.hip', 'k6_dp.hip', 'k6_trace.hip', 'k6_paths.hip', 'k9_path_stats.hip', 'k10_window_stats.hip', 'k11_path_text.hip', 'k12_link_regions.hip', 'k17_terminal.hip']
+FILES = ['k34_fused.hip', 'k4_extend.hip', 'k5_chain.hip', 'k5_wave.hip', 'k6_gapped.hip', 'k6_dp.hip', 'k6_trace.hip', 'k6_paths.hip', 'k9_path_stats.hip', 'k10_window_stats.hip', 'k11_path_text.hip', 'k12_link_regions.hip', 'k17_terminal.hip', 'k18_flank.hip', 'k19_frames.hip']
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off', '-w', '-S', '--cuda-device-only']
 # kernels (name without template arguments) that may keep flat_* accesses, each with its reason
 ALLOW = {
