@@ -924,6 +924,19 @@ int mimeo_coverage_bedgraph(const mimeo_interval *iv, uint64_t n, const uint32_t
 int mimeo_tandem_masked(const mimeo_genome *A, const mimeo_interval *iv, uint64_t n, int32_t match,
                         int32_t mismatch, int32_t delta, int32_t minscore, int32_t maxperiod, uint32_t *masked);
 
+/*
+ * The same call with the positions: besides masked[k], the bit masks the device holds for the slices, the very words
+ * the counts are summed from (one device call serves both entry points).  Slice k, clipped to its scaffold, has
+ * len_k = min(end, scaffold length) - start bases (0 if start is not below that: an empty or inverted slice) and owns
+ * (len_k + 31) / 32 consecutive words, the slices following one another in the order of iv; bit i % 32 of a slice's
+ * word i / 32 is set when base start + i is marked, and the bits from len_k on in its last word are zero.  *words is
+ * allocated by the library (free with mimeo_free; never null on success, also for *nwords = 0), *nwords is their total.
+ * Everything else is as for mimeo_tandem_masked.
+ */
+int mimeo_tandem_mask(const mimeo_genome *A, const mimeo_interval *iv, uint64_t n, int32_t match, int32_t mismatch,
+                      int32_t delta, int32_t minscore, int32_t maxperiod, uint32_t *masked, uint32_t **words,
+                      uint64_t *nwords);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ SYMBOLS = [
     'mimeo_path_window_stats', 'mimeo_path_text', 'mimeo_link_regions', 'mimeo_path_pileup',
     'mimeo_path_insertions', 'mimeo_path_stack', 'mimeo_path_call_stats', 'mimeo_terminal_params_default',
     'mimeo_terminal_repeats', 'mimeo_flank_params_default', 'mimeo_flank_repeats', 'mimeo_open_frames',
+    'mimeo_tandem_mask',
 ]
 
 
@@ -172,6 +173,9 @@ def load():
         lib.mimeo_coverage_bedgraph.argtypes = [vp, u64, vp, u32, C.POINTER(vp), C.POINTER(u64)]
     if hasattr(lib, 'mimeo_tandem_masked'):
         lib.mimeo_tandem_masked.argtypes = [vp, vp, u64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
+    if hasattr(lib, 'mimeo_tandem_mask'):
+        lib.mimeo_tandem_mask.argtypes = [vp, vp, u64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.POINTER(vp),
+                                          C.POINTER(u64)]
     if lib.mimeo_abi_version() != ABI_VERSION:
         raise RuntimeError('libmimeo_hip.so ABI %d != expected %d' % (lib.mimeo_abi_version(), ABI_VERSION))
     _lib = lib

@@ -582,4 +582,19 @@ int mimeo_tandem_masked(const mimeo_genome *A, const mimeo_interval *iv, uint64_
     return tandem_masked_device(A, iv, n, match, mismatch, delta, minscore, maxperiod, masked);
 }
 
+int mimeo_tandem_mask(const mimeo_genome *A, const mimeo_interval *iv, uint64_t n, int32_t match, int32_t mismatch,
+                      int32_t delta, int32_t minscore, int32_t maxperiod, uint32_t *masked, uint32_t **words, uint64_t *nwords) {
+    int rc = need_init();
+    if (rc) return rc;
+    if (!A || !words || !nwords || (n && (!iv || !masked))) { set_error("null argument"); return MIMEO_ERR_ARG; }
+    std::vector<uint32_t> res;
+    if ((rc = tandem_masked_device(A, iv, n, match, mismatch, delta, minscore, maxperiod, masked, &res))) return rc;
+    uint32_t *r = (uint32_t *)malloc((res.size() ? res.size() : 1) * sizeof(uint32_t));
+    if (!r) { set_error("host allocation failed"); return MIMEO_ERR_NOMEM; }
+    if (!res.empty()) memcpy(r, res.data(), res.size() * sizeof(uint32_t));
+    *words = r;
+    *nwords = res.size();
+    return MIMEO_OK;
+}
+
 }  // extern "C"

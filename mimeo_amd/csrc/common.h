@@ -352,9 +352,10 @@ int ungapped_units(const std::vector<UnitWork> &work, const mimeo_params *p, std
                    ExtStats *st);  // pipeline.hip: the extension stage of a batch, HSPs per unit on the host
 int build_kept_indexes(mimeo_genome *g, const uint32_t *scaf, uint64_t n);  // pipeline.hip
 
-// K8: tandem scorer (k8_tandem.hip); host in, host out
+// K8: tandem scorer (k8_tandem.hip); host in, host out.  h_words (optional): the slices' mask words, the very words
+// k8_tandem_count sums into h_masked; slice k owns (clipped length + 31) / 32 of them, in slice order.
 int tandem_masked_device(const mimeo_genome *A, const mimeo_interval *h_iv, uint64_t n, int match, int mismatch, int delta,
-                         int minscore, int maxperiod, uint32_t *h_masked);
+                         int minscore, int maxperiod, uint32_t *h_masked, std::vector<uint32_t> *h_words = nullptr);
 
 // K9: column statistics of alignment paths (k9_path_stats.hip); host in, host out.  Q is never null here.
 int path_stats_device(const mimeo_genome *T, const mimeo_genome *Q, const mimeo_alignment *aln, uint64_t n, const uint64_t *first,

@@ -212,7 +212,8 @@ __global__ void k8_tandem_count(const mimeo_interval *__restrict__ iv, uint64_t 
 }
 
 int tandem_masked_device(const mimeo_genome *A, const mimeo_interval *h_iv, uint64_t n, int match, int mismatch, int delta,
-                         int minscore, int maxperiod, uint32_t *h_masked) {
+                         int minscore, int maxperiod, uint32_t *h_masked, std::vector<uint32_t> *h_words) {
+    if (h_words) h_words->clear();
     if (!n) return 0;
     if (maxperiod < 1 || maxperiod > host_plan::TANDEM_MAXPERIOD) { set_error("tandem scorer: maxperiod must be in 1..2000"); return MIMEO_ERR_LIMIT; }
     const bool wide = maxperiod > (int)host_plan::TANDEM_BLOCK;
@@ -259,6 +260,10 @@ int tandem_masked_device(const mimeo_genome *A, const mimeo_interval *h_iv, uint
     hipLaunchKernelGGL(k8_tandem_count, dim3(nb), dim3(256), 0, st, (const mimeo_interval *)di.p, n,
                        (const uint64_t *)dof.p, (const uint32_t *)db.p, (uint32_t *)dm.p);
     HIP_TRY(hipMemcpyAsync(h_masked, dm.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (h_words) {   // the words k8_tandem_count has just summed: slice k owns off[k] .. off[k + 1]
+        h_words->resize(off[n]);
+        if (off[n]) HIP_TRY(hipMemcpyAsync(h_words->data(), db.p, off[n] * 4, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipGetLastError());
     for (DeviceBuf *b : {&dv, &di, &dof, &db, &dm, &dj}) b->release();

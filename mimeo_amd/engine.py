@@ -577,3 +577,33 @@ def tandem_masked(A, intervals, match=2, mismatch=7, minscore=50, maxperiod=50, 
         _ffi.check(_ffi.load().mimeo_tandem_masked(A._h, iv.ctypes.data, iv.size, int(match), int(mismatch), int(delta),
                                                    int(minscore), int(maxperiod), out.ctypes.data))
     return out
+
+
+def tandem_mask(A, intervals, match=2, mismatch=7, minscore=50, maxperiod=50, delta=7, counts=False):
+    """The positions behind tandem_masked, from the same device call: one bool array per slice, as long as the slice
+    clipped to its scaffold (empty for an empty or inverted slice); element i says whether base start + i is marked.
+    counts=True: (masks, the uint32 counts the device summed from the same words)."""
+    iv = np.asarray(intervals)
+    if iv.dtype != _ffi.INTERVAL:
+        a = np.asarray(iv, dtype=np.uint32).reshape(-1, 3)
+        iv = np.zeros(a.shape[0], dtype=_ffi.INTERVAL)
+        iv['chrom'], iv['start'], iv['end'] = a[:, 0], a[:, 1], a[:, 2]
+    iv = np.ascontiguousarray(iv)
+    out = np.zeros(iv.size, dtype=np.uint32)
+    ptr, n = C.c_void_p(), C.c_uint64()
+    _ffi.check(_ffi.load().mimeo_tandem_mask(A._h, iv.ctypes.data if iv.size else None, iv.size, int(match), int(mismatch), int(delta),
+                                             int(minscore), int(maxperiod), out.ctypes.data if iv.size else None, C.byref(ptr),
+                                             C.byref(n)))
+    words = _ffi.take(ptr, n, np.dtype('<u4'))
+    masks, w = [], 0
+    for c, s, e in iv.tolist():
+        ln = max(0, min(e, A.lengths[c]) - s)
+        nw = (ln + 31) // 32
+        bits = np.unpackbits(words[w:w + nw].view(np.uint8), bitorder='little')
+        if bits[ln:].any():
+            raise RuntimeError('tandem scorer: a slice mask has bits beyond its slice')
+        masks.append(bits[:ln].astype(bool))
+        w += nw
+    if w != words.size:
+        raise RuntimeError('tandem scorer: %d mask words for slices of %d' % (words.size, w))
+    return (masks, out) if counts else masks

@@ -163,7 +163,7 @@ def gff_map_lines(rows, chromlens, ftype='BHit'):
     return lines
 
 
-def tandem_masked(seq, start, end, match=2, mismatch=7, minscore=50, maxperiod=50, delta=7):
+def tandem_masked(seq, start, end, match=2, mismatch=7, minscore=50, maxperiod=50, delta=7, return_mask=False):
     """CPU restatement of the tandem scorer v2 that stands in for
     `trf F 2 7 7 80 10 50 50 -m -h -ngs` in wrappers.py:120-262.  PARITY UNPINNED: TRF itself is
     absent; this restates OUR specification, not TRF's heuristics.  For every period p the slice is
@@ -172,7 +172,8 @@ def tandem_masked(seq, start, end, match=2, mismatch=7, minscore=50, maxperiod=5
       H[j][d] = max(0, H[j-1][d] + s(S[j], S[j-d]), H[j-1][d-1] - delta, H[j][d+1] - delta)
     (ties: diagonal, insertion, deletion); a path that reaches a new best >= minscore masks everything
     from the first base of its earlier copy to the base it has reached.  seq: bytes; returns the
-    number of masked bases of seq[start:end]."""
+    number of masked bases of seq[start:end], or with return_mask the mask itself (a bytearray of
+    0 / 1, one per base of the slice)."""
     s = seq[start:end].upper()
     L = len(s)
     masked = bytearray(L)
@@ -209,7 +210,7 @@ def tandem_masked(seq, start, end, match=2, mismatch=7, minscore=50, maxperiod=5
                         c = (h, st, h, mend)
                 cur[k] = c
             prev = cur
-    return sum(masked)
+    return masked if return_mask else sum(masked)
 
 
 def trf_filter(rows, seq_of, prefix=None, tmatch=2, tmismatch=7, tminscore=50, tmaxperiod=50, maxtandem=40, masked_fn=None, tdelta=7):

@@ -55,8 +55,13 @@ def test_tandem_masked_equals_cpu_restatement(eng):
     # (match, mismatch, minscore, maxperiod, delta): TRF's defaults, variations, and delta 0 = the gap-free scorer
     for params in ((2, 7, 50, 50, 7), (2, 5, 30, 12, 3), (3, 7, 80, 64, 9), (2, 7, 50, 50, 0)):
         got = eng.tandem_masked(g, np.array(iv, dtype=np.uint32), *params)
-        exp = [P.tandem_masked(seqs[c].tobytes(), s, min(e, len(seqs[c])), *params) for c, s, e in iv]
+        exp_mask = [np.array(P.tandem_masked(seqs[c].tobytes(), s, min(e, len(seqs[c])), *params, return_mask=True), dtype=bool)
+                    for c, s, e in iv]
+        exp = [int(m.sum()) for m in exp_mask]
         assert got.tolist() == exp, params
+        masks = eng.tandem_mask(g, np.array(iv, dtype=np.uint32), *params)     # the positions, not only how many
+        for k, (m, x) in enumerate(zip(masks, exp_mask)):
+            assert m.shape == x.shape and np.array_equal(m, x), (params, iv[k], np.flatnonzero(m != x)[:8].tolist())
     g.close()
 
 

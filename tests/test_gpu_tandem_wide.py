@@ -68,14 +68,14 @@ def edge_scaffold():
     return s, spans
 
 
-def _oracle(seqs, iv, params, memo=None):
+def _oracle(seqs, iv, params, memo=None, return_mask=False):
     from oracle import pipeline as P
     memo = {} if memo is None else memo
     out = []
     for c, s, e in iv:
         if (c, s, e) not in memo:
-            memo[(c, s, e)] = P.tandem_masked(seqs[c].tobytes(), s, min(e, len(seqs[c])), *params)
-        out.append(memo[(c, s, e)])
+            memo[(c, s, e)] = np.array(P.tandem_masked(seqs[c].tobytes(), s, min(e, len(seqs[c])), *params, return_mask=True), dtype=bool)
+        out.append(memo[(c, s, e)] if return_mask else int(memo[(c, s, e)].sum()))
     return out
 
 
@@ -95,9 +95,13 @@ def test_block_edges_equal_cpu_restatement(eng, edge_scaffold, params):
     assert sum(min(e, n) - s for _, s, e in iv) * params[3] < 1.5e6             # the restatement's work, kept small
     g = eng.Genome(['edge'], [seq])
     got = eng.tandem_masked(g, np.array(iv, dtype=np.uint32), *params)
+    masks = eng.tandem_mask(g, np.array(iv, dtype=np.uint32), *params)
     g.close()
-    exp = _oracle([seq], iv, params)
+    memo = {}
+    exp = _oracle([seq], iv, params, memo)
     assert got.tolist() == exp, params
+    for k, (m, x) in enumerate(zip(masks, _oracle([seq], iv, params, memo, return_mask=True))):   # the positions, not only how many
+        assert m.shape == x.shape and np.array_equal(m, x), (params, iv[k], np.flatnonzero(m != x)[:8].tolist())
     if params[3] >= 128 and params[4] > 0:
         assert sum(exp[:7]) > 0.85 * sum(b - a for a, b in spans)               # the arrays are what is being masked
 

@@ -23,6 +23,7 @@ def test_header_symbols_are_exported():
     declared = set(re.findall(r'\b(mimeo_[a-z_]+)\s*\(', hdr))
     from mimeo_amd import _ffi
     assert declared == set(_ffi.SYMBOLS)
+    assert {'mimeo_tandem_masked', 'mimeo_tandem_mask'} <= declared   # K8: the counts, and the counts with the positions
     for s in declared:
         assert hasattr(lib, s), s
     assert lib.mimeo_abi_version() == _ffi.ABI_VERSION == 3
